@@ -1,7 +1,14 @@
 """Benchmark: implicit-ALS interactions/sec per sweep (BASELINE.json metric) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline value,
+ms_per_step, and what the timed steps' own event timers give: stages, paths, the solve roofline).
+--dump-outputs DIR then writes what the last timed step computed (DIR/user_factors.npy,
+DIR/item_factors.npy; a fixed seeded row sample when the factors exceed the size cap).  --full adds
+everything that takes a run of its own: the top-30 run, the CPU baseline, the degree census and the
+committed counter profiles (--no-cpu / --topk-users 0 still drop the first two there).
 
 A step = one full ALS sweep (item half-sweep + user half-sweep: Gram, eigendecomposition,
 rotation, RCCL all-reduce/all-gather, light + heavy per-row solves) over the whole synthetic star
@@ -47,7 +54,38 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--light", type=int, default=-1)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the top-30 run, the CPU baseline, "
+                         "the degree census, the committed counter profiles")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SIDE_BYTES = 24 << 20  # per side; both sides together stay well under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(lib, L, h, k, out_dir, write=True):
+    """The factors of both sides after the last timed step, as a caller reads them (als_get_factors:
+    original basis, ascending id order), float32.  A side larger than DUMP_SIDE_BYTES is written as a
+    fixed seeded sample of its rows (ascending positions), the same rows in every run and build."""
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+    for side, name in ((0, "user_factors"), (1, "item_factors")):
+        n = lib.als_num_rows(h, side)
+        f = np.empty((n, k), np.float32)
+        L.check(lib.als_get_factors(h, side, None, L.ptr(f, C.c_float)))
+        cap = max(1, DUMP_SIDE_BYTES // (4 * k))
+        if n > cap:
+            rows = np.sort(np.random.default_rng(DUMP_SEED + side).choice(n, size=cap, replace=False))
+            f = f[rows]
+        if write:
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(f))
+        del f
 
 
 def main():
@@ -94,11 +132,13 @@ def main():
     setup_s = time.perf_counter() - t0
     nnz = lib.als_num_ratings(h)
     n_users, n_items = lib.als_num_rows(h, 0), lib.als_num_rows(h, 1)
-    top_deg = {}
-    for side, name in ((0, "users"), (1, "repos")):
-        dg = np.empty(lib.als_num_rows(h, side), np.int64)
-        L.check(lib.als_get_degrees(h, side, L.ptr(dg, C.c_int64)))
-        top_deg[name] = np.sort(dg[dg >= 0])[::-1][:5].tolist()
+    top_deg = None
+    if args.full:  # degree census: a D2H copy and a sort of every row's degree
+        top_deg = {}
+        for side, name in ((0, "users"), (1, "repos")):
+            dg = np.empty(lib.als_num_rows(h, side), np.int64)
+            L.check(lib.als_get_degrees(h, side, L.ptr(dg, C.c_int64)))
+            top_deg[name] = np.sort(dg[dg >= 0])[::-1][:5].tolist()
 
     def barrier():
         L.check(lib.als_synchronize(h))
@@ -122,6 +162,11 @@ def main():
         stage[0] += tt
     barrier()
     elapsed = time.perf_counter() - t_start
+    dump_s = None
+    if args.dump_outputs:  # every rank takes part (the factors are gathered); rank 0 writes
+        t0 = time.perf_counter()
+        dump_outputs(lib, L, h, k, args.dump_outputs, write=rank == 0)
+        dump_s = time.perf_counter() - t0
     nnls_iters, eig_sweeps = {}, {}
     for side in (0, 1):
         L.check(lib.als_path_stats(h, side, L.ptr(stats[side], C.c_int64)))
@@ -213,7 +258,7 @@ def main():
             if os.path.exists(path):
                 return path
         return None
-    spath = latest("sq_counters")
+    spath = latest("sq_counters") if args.full else None
     if spath:
         sj = json.load(open(spath))
         mfma_evidence = {"source": os.path.relpath(spath, ROOT)}
@@ -235,7 +280,7 @@ def main():
     # its slice against the replicated dst factors, the lists are all-gathered); timed between
     # barriers, max over ranks
     topk_ups = topk_info = None
-    if args.topk_users != 0:
+    if args.full and args.topk_users != 0:
         ids = np.empty(n_users, np.int32)
         L.check(lib.als_get_ids(h, 0, L.ptr(ids, C.c_int32)))
         every = args.topk_users < 0 or args.topk_users >= n_users
@@ -284,7 +329,7 @@ def main():
                              "MFMA scan with norm-order early exit, exact F2J rescoring, D2H of the lists"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         if args.config in NONNEGATIVE:
             cpu = cpu_baseline_nnls(lib, L, h, k, nnz, n_users, n_items, args.cpu_seconds)
         else:
@@ -319,6 +364,8 @@ def main():
             "nnls_iterations_last_sweep": nnls_iters or None,
             "eig_jacobi_sweeps_last_sweep": eig_sweeps or None,
             "setup_s": setup_s,
+            "full": args.full,
+            "dump_outputs": args.dump_outputs and {"dir": args.dump_outputs, "seconds": dump_s},
         }
         print(json.dumps(line), flush=True)
     lib.als_destroy(h)
