@@ -50,7 +50,7 @@ class Ctx:
         p.light_max_degree, p.max_iter = light, max_iter
         self.h = C.c_void_p()
         L.check(lib.als_create(C.byref(p), C.byref(self.h)))
-        self.rank = rank
+        self.rank, self.light = rank, light
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -647,6 +647,7 @@ def _check_rows_fp64(gpu_lib, c, side, rows_ids, X_ids, X, Y_ids, Y, k, gram=Non
     """Rows `rows_ids` of `side` (solved into X) equal the fp64 solve of Spark's implicit normal
     equation from the src factors Y, built from the engine's own CSR; returns the worst error."""
     from albedo_amd import _lib as L
+    from tests.ladder import padded_rank, path_of, split_chunk
     G = _gram_fp64(Y) if gram is None else gram
     n_row = np.empty(1, np.int64)
     worst = 0.0
@@ -664,7 +665,8 @@ def _check_rows_fp64(gpu_lib, c, side, rows_ids, X_ids, X, Y_ids, Y, k, gram=Non
         b = Yr.T @ np.where(rat[:n] > 0, 1.0 + cvec, 0.0)
         x = np.linalg.solve(A, b)
         err = np.max(np.abs(X[np.searchsorted(X_ids, rid)] - x)) / np.max(np.abs(x))
-        assert err < 1e-4, f"side {side} id {rid} ({n} ratings): rel err {err:.3e}"
+        assert err < 1e-4, (f"side {side} id {rid} ({n} ratings, path "
+                            f"{path_of(n, padded_rank(c.rank), c.light, split_chunk())}): rel err {err:.3e}")
         worst = max(worst, float(err))
     return worst
 

@@ -174,3 +174,173 @@ def test_c_nnls_matches_numpy_nnls_on_f5():
     U_ref = O.half_sweep(V, B.u_ptr, B.u_col, B.u_val, reg=0.5, alpha=40.0, nonnegative=True)
     assert np.allclose(U, U_ref, rtol=1e-6, atol=1e-7)
     assert np.mean((U == 0) == (U_ref == 0)) == 1.0
+
+
+# ---- rating modes: non-unit, signed and zero ratings (tests/test_gpu_rating_modes.py relies on these) ----
+
+def _signed_small_set():
+    """A small set with non-unit, negative and exactly-zero ratings, and rows without a positive one."""
+    from albedo_amd.synthetic import SynthSpec, generate
+    d = generate(SynthSpec(300, 120, 3000, seed=6))
+    rng = np.random.default_rng(6)
+    r = rng.choice([0.25, 0.5, 1.0, 2.0, 3.0, 5.0], d["user"].size)
+    r[rng.random(r.size) < 0.15] = 0.0
+    r = np.where(rng.random(r.size) < 0.25, -r, r) + 0.0
+    nonpos = np.isin(d["item"], np.unique(d["item"])[:3])
+    r[nonpos] = -np.abs(r[nonpos]) + 0.0
+    B = O.make_blocks(d["user"], d["item"], r)
+    assert (B.i_val < 0).any() and (B.i_val == 0).any()
+    npos = np.add.reduceat(B.i_val > 0, B.i_ptr[:-1])
+    assert (npos == 0).any() and (npos > 0).any()
+    return B
+
+
+@pytest.mark.parametrize("implicit", [True, False], ids=["implicit", "explicit"])
+def test_c_oracle_matches_numpy_oracle_on_signed_nonunit_ratings(implicit):
+    """cbind.half_sweep (Cholesky) and cbind.solve_rows_nnls against the numpy oracle on non-unit,
+    negative and zero ratings, implicit and explicit, both halves (tolerances of
+    test_numpy_oracle_matches_c_oracle / test_c_nnls_matches_numpy_nnls_on_f5)."""
+    B = _signed_small_set()
+    rng = np.random.default_rng(7)
+    alpha, reg = (10.0, 0.5) if implicit else (1.0, 0.1)
+    for ptr, col, val, n_src in ((B.i_ptr, B.i_col, B.i_val, len(B.user_ids)), (B.u_ptr, B.u_col, B.u_val, len(B.item_ids))):
+        Y = rng.standard_normal((n_src, 12)).astype(np.float32)
+        a = O.half_sweep(Y, ptr, col, val, reg=reg, alpha=alpha, implicit=implicit)
+        b = cbind.half_sweep(Y, ptr, col, val, reg=reg, alpha=alpha, implicit=implicit)
+        assert np.allclose(a, b, rtol=1e-6, atol=1e-7)
+        Yn = np.abs(Y)
+        Yn[:, ::5] *= -1.0
+        a = O.half_sweep(Yn, ptr, col, val, reg=reg, alpha=alpha, implicit=implicit, nonnegative=True)
+        b, it = cbind.solve_rows_nnls(Yn, O.gram(Yn), ptr, col, val, reg=reg, alpha=alpha, implicit=implicit, threads=3)
+        assert np.all(b >= 0) and (a == 0).any() and (a > 0).any()
+        assert np.allclose(a, b, rtol=1e-6, atol=1e-7)
+        assert np.mean((a == 0) == (b == 0)) == 1.0
+
+
+def _solve_rows64(Y, ptr, col, val, implicit, alpha, reg, mistake=None):
+    """fp64 solutions of Spark's normal equations, row by row; `mistake` restates one plausible kernel
+    bug: "mask_zero" (explicit ratings of 0 left out of A), "cmax" (every implicit confidence taken
+    as alpha·max|r|), "nosign" (the sign of r ignored in b's weight)."""
+    Y = np.asarray(Y, np.float64)
+    k = Y.shape[1]
+    G = Y.T @ Y if implicit else np.zeros((k, k))
+    rmax = float(np.max(np.abs(val)))
+    X = np.zeros((len(ptr) - 1, k))
+    for j in range(len(ptr) - 1):
+        Yj = Y[col[ptr[j]:ptr[j + 1]]]
+        r = val[ptr[j]:ptr[j + 1]].astype(np.float64)
+        if implicit:
+            c = alpha * (np.full(r.size, rmax) if mistake == "cmax" else np.abs(r))
+            w = np.where((r != 0) if mistake == "nosign" else (r > 0), 1.0 + c, 0.0)
+            n = int(np.sum(r > 0))
+        else:
+            c = np.where(r == 0, 0.0, 1.0) if mistake == "mask_zero" else np.ones(r.size)
+            w, n = r, r.size
+        X[j] = np.linalg.solve(G + (Yj.T * c) @ Yj + reg * n * np.eye(k), Yj.T @ w)
+    return X
+
+
+@pytest.mark.parametrize("mode,mistake", [("stars_signed", "mask_zero"), ("varying", "cmax"), ("mixed", "cmax"),
+                                          ("signed_uniform", "nosign"), ("mixed", "nosign")])
+def test_ladder_inputs_expose_wrong_rating_weights(mode, mistake):
+    """The ladder inputs tell a kernel with a plausible rating-weight bug from a right one: on every
+    row the bug touches (with a non-zero solution, or a zero one the bug makes non-zero) the mistaken
+    fp64 solution is more than 10x the GPU tolerance (1e-4) away from the oracle's: item half at ranks
+    50 / 128 / 256.  On the user half (rank 50, from the oracle's own item factors, whose rows differ in
+    size by orders of magnitude) the same holds for more than 90 % of the touched rows."""
+    from tests import ladder as LD
+    implicit, alpha, reg = LD.MODES[mode]
+    user, item, ideg = LD.ladder_coo()
+    B = O.make_blocks(user, item, LD.ladder_ratings(mode, user, ideg))
+
+    def touched(Y, col, val, ptr):  # a rating the bug treats differently, on a src row that is not all zero
+        hit = {"mask_zero": val == 0, "cmax": np.abs(val) != np.max(np.abs(val)), "nosign": val < 0}[mistake]
+        return np.add.reduceat(hit & Y[col].any(axis=1), ptr[:-1]) > 0
+
+    def check(Y, ptr, col, val, what, every=True):
+        good = _solve_rows64(Y, ptr, col, val, implicit, alpha, reg)
+        ref = O.half_sweep(Y, ptr, col, val, reg=reg, alpha=alpha, implicit=implicit)
+        assert LD.row_errors(good, ref).max() < 1e-6  # the helper restates the oracle
+        dev = LD.row_errors(_solve_rows64(Y, ptr, col, val, implicit, alpha, reg, mistake), good)
+        rows = touched(Y, col, val, ptr) & (good.any(axis=1) | (dev > 0))
+        assert rows.sum() >= 20, what
+        if every:
+            assert dev[rows].min() > 10 * 1e-4, (what, float(dev[rows].min()))
+        assert np.mean(dev[rows] > 10 * 1e-4) > 0.9, what
+        return ref
+
+    for k in (50, 128, 256):
+        V = check(LD.unit_rows(np.random.default_rng(k), len(B.user_ids), k), B.i_ptr, B.i_col, B.i_val, f"item k={k}")
+        if k == 50:
+            check(V, B.u_ptr, B.u_col, B.u_val, "user k=50", every=False)
+
+
+def test_ladder_data_and_path_labels():
+    """The ladder holds every degree twice, every configuration's expected paths have at least 2 rows
+    on the item side (and light16 pairs, light16 and D = 32 on the user side), `mixed` has at least 4
+    item rows without a positive rating, and every user keeps a positive rating in the implicit modes."""
+    from tests import ladder as LD
+    user, item, ideg = LD.ladder_coo()
+    assert 6000 < user.size < 7500 and np.any(np.diff(user) < 0)  # shuffled COO
+    assert np.unique(user.astype(np.int64) << 32 | item).size == user.size
+    assert np.max(np.diff(np.unique(user))) > 1  # sparse raw ids
+    B = O.make_blocks(user, item, np.ones(user.size, np.float32))
+    deg_i, deg_u = np.diff(B.i_ptr), np.diff(B.u_ptr)
+    assert sorted(deg_i.tolist()) == sorted(LD.LADDER + LD.LADDER)
+    assert 650 <= len(B.user_ids) <= 700 and 16 < deg_u.max() <= 32
+    assert LD.path_of(8, 64, -1, 8192) == "light16-pair" and LD.path_of(9, 64, -1, 8192) == "light16"
+    assert LD.path_of(32, 64, -1, 8192) == "light32" and LD.path_of(33, 64, -1, 8192) == "wave"
+    assert LD.path_of(64, 128, -1, 8192) == "light64" and LD.path_of(65, 128, -1, 8192) == "wave"
+    assert LD.path_of(96, 128, 96, 8192) == "light96" and LD.path_of(97, 128, 96, 8192) == "wave"
+    assert LD.path_of(64, 256, -1, 8192) == "light64" and LD.path_of(65, 256, 96, 8192) == "heavy"
+    assert LD.path_of(256, 256, -1, 256) == "heavy" and LD.path_of(257, 256, -1, 256) == "split"
+    assert LD.path_of(1, 128, 0, 256) == "wave" and LD.path_of(257, 128, 0, 0) == "wave"
+    for k, light, chunk in LD.CONFIGS:
+        KP, ch = LD.padded_rank(k), LD.split_chunk(chunk or "8192")
+        for deg in (deg_i, deg_u):
+            paths = np.array([LD.path_of(d, KP, light, ch) for d in deg])
+            want = LD.expected_paths(KP, light, ch, int(deg.max()))
+            assert set(paths.tolist()) == set(want), (k, light, chunk)
+            assert all(np.sum(paths == p) >= 2 for p in want), (k, light, chunk)
+    for mode, (implicit, _, _) in LD.MODES.items():
+        r = LD.ladder_ratings(mode, user, ideg)
+        if implicit:
+            assert np.isin(user, user[r > 0]).all(), mode
+        if mode == "mixed":
+            Bm = O.make_blocks(user, item, r)
+            npos = np.add.reduceat(Bm.i_val > 0, Bm.i_ptr[:-1])
+            assert np.sum(npos == 0) >= 4
+            assert set(np.diff(Bm.i_ptr)[npos == 0].tolist()) >= set(LD.NONPOS_DEGREES)
+        if mode in ("mixed", "stars_signed"):
+            assert 0.08 < np.mean(r == 0) < 0.2 and (r < 0).any()
+        if mode == "signed_uniform":
+            assert set(np.unique(r).tolist()) == {-2.0, 2.0} and 0.2 < np.mean(r < 0) < 0.35
+
+
+def test_assert_rows_names_the_failing_row(tmp_path):
+    """The failure report of the rating-mode tests: one row off by 1 % is named with its raw id, degree
+    and path label, and its got / ref are saved; an all-zero reference row must be exactly zero."""
+    from tests import ladder as LD
+    rng = np.random.default_rng(8)
+    ref = rng.standard_normal((40, 16)).astype(np.float32)
+    ref[5] = 0.0
+    ids = np.arange(40, dtype=np.int32) * 37 + 1000
+    deg = np.arange(40) + 1
+    paths = [LD.path_of(d, 128, -1, 8192) for d in deg]
+    got = ref + 1e-6 * np.abs(ref).max(axis=1, keepdims=True) * rng.uniform(-1, 1, ref.shape).astype(np.float32)
+    assert LD.assert_rows(got, ref, ids, deg, paths, 1e-4, "clean", tmp_path) < 2e-6
+    got[17] *= 1.01
+    with pytest.raises(AssertionError) as e:
+        LD.assert_rows(got, ref, ids, deg, paths, 1e-4, "item half [mixed-k128]", tmp_path)
+    msg = str(e.value)
+    assert "1 of 40 rows" in msg and f"id {ids[17]} degree 18 path light32" in msg and "item half [mixed-k128]" in msg
+    saved = np.load(msg.rsplit("saved to ", 1)[1].strip())
+    assert saved["ids"].tolist() == [ids[17]] and saved["deg"].tolist() == [18]
+    assert np.array_equal(saved["got"][0], got[17]) and np.array_equal(saved["ref"][0], ref[17])
+    got[17] = ref[17]
+    got[5, 3] = 1e-30
+    with pytest.raises(AssertionError, match=f"id {ids[5]} degree 6 path light16-pair"):
+        LD.assert_rows(got, ref, ids, deg, paths, 1e-4, "zero row", tmp_path)
+    got[5, 3] = np.nan
+    with pytest.raises(AssertionError, match=f"id {ids[5]} "):
+        LD.assert_rows(got, ref, ids, deg, paths, 1e-4, "nan", tmp_path)
