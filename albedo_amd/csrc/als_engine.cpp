@@ -1659,7 +1659,8 @@ int topk_dst_basis(als_ctx* c, const double* Gf, std::vector<double>& VP) {
   for (int i = 0; i < k; ++i)
     for (int j = 0; j < k; ++j) Gk[(size_t)i * k + j] = Gf[(size_t)i * KP + j];
   if (!sym_eig(k, Gk.data(), w.data(), V.data()))
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE, "eigendecomposition of the dst Gram matrix did not converge");
+    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
+                "the dst Gram matrix is not finite (row norms above ~2^63) or its eigendecomposition did not converge");
   std::vector<int> idx(k);
   std::iota(idx.begin(), idx.end(), 0);
   std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return w[a] > w[b]; });

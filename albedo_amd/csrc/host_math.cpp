@@ -101,7 +101,9 @@ static bool tql2(int n, double* V, double* d, double* e) {
   for (int l = 0; l < n; l++) {
     tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
     int m = l;
-    while (m < n) {
+    // e[n - 1] = 0 ends the search at n - 1 for finite input; the bound keeps m inside d / e / V when a
+    // NaN (an overflow inside tred2) makes every comparison false: the iteration cap then returns false
+    while (m < n - 1) {
       if (std::fabs(e[m]) <= eps * tst1) break;
       m++;
     }
@@ -174,6 +176,9 @@ static void transpose(int n, double* V) {
 }
 
 bool sym_eig(int n, const double* a, double* w, double* v) {
+  // a non-finite matrix (a Gram whose fp32 partial sums overflowed) has no decomposition: say so
+  for (size_t i = 0; i < (size_t)n * n; ++i)
+    if (!std::isfinite(a[i])) return false;
   std::memcpy(v, a, sizeof(double) * n * n);
   std::vector<double> e(n, 0.0);
   if (n == 1) {

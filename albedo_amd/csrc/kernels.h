@@ -159,7 +159,7 @@ struct TopkArgs {
   int64_t n_chunks;
   const double* VP;        // [TOPK_M][KP] leading eigenvectors of the dst Gram (fp64)
   const float* cfeat;      // [n_chunks][TOPK_CF] chunk bound boxes (null: no pruning)
-  const void* probe;       // [256][KP] fp16 probe rows (the largest norms), ·tsc, zero rows past n_dst
+  const void* probe;       // [TOPK_NPROBE][KP] fp16 probe rows (the largest norms), ·tsc, zero rows past n_dst
   const float* sfeat;      // [n_src][TOPK_SF] src features by scan position (order kernel output)
   const uint32_t* mask;    // [n_wg][mask_words] needed chunks per scan workgroup (null: every chunk)
   int64_t mask_words;
@@ -202,7 +202,7 @@ int topk_chunk_rows(int KP);    // dst rows per scan chunk (Th / cfeat are padde
 size_t topk_sort_temp_bytes(int64_t n_dst);
 // VP: [TOPK_M][KP] fp64 (device); keys: 4·n uint32, perm / nperm: 2·n uint32 ([0, n) is the result:
 // scan order / descending norm), tp: [n][TOPK_M] fp64 scratch, Th / cfeat / supf (super-chunk boxes)
-// as above, probe: [256][KP] fp16
+// as above, probe: [TOPK_NPROBE][KP] fp16
 hipError_t topk_prepare(int KP, int kreal, const float* T, int64_t n_dst, float tsc, const double* VP, void* temp,
                         size_t temp_bytes, uint32_t* keys, uint32_t* perm, uint32_t* nperm, double* tp, void* Th,
                         float* cfeat, float* supf, void* probe, hipStream_t s);

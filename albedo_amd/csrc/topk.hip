@@ -8,8 +8,8 @@
 //           most of their energy in one or two directions (c4: 84 % / 92 %), so the bound is tight:
 //           at c4 it keeps < 1 % of the dst chunks of a user against the 64th best score.
 //  prepare  dst rows by descending ‖t_⊥‖ (device radix sort), packed as fp16 rows scaled by a power of
-//           two, CH-row chunks with their box + R (and 16-chunk super-chunks), a probe image of the 256
-//           largest-norm rows;
+//           two, CH-row chunks with their box + R (and 16-chunk super-chunks), a probe image of the
+//           TOPK_NPROBE (512) largest-norm rows;
 //  order    one wave per 16 src rows: scores against the probe rows on MFMA, the kt-th best v* -> the
 //           starting threshold thr0 = v* minus the rounding difference to the scan; the src features
 //           (s_P, ‖s_⊥‖, the pruning margin); a sort key that groups rows of similar depth and
@@ -728,8 +728,8 @@ __device__ __forceinline__ void topk_select_row(const TopkArgs& a, int64_t si, i
 
 
 // Scan order, starting thresholds and features of the src rows.  One wave per 16 src rows scores them
-// against the probe rows (the 256 largest-norm dst rows, fp16 like the scan) on MFMA and finds each
-// row's exact kt-th best v* of those 256 by bisection on order-preserving keys.  thr0 = v* minus the
+// against the probe rows (the TOPK_NPROBE = 512 largest-norm dst rows, fp16 like the scan) on MFMA and
+// finds each row's exact kt-th best v* of those by bisection on order-preserving keys.  thr0 = v* minus the
 // accumulation difference between this pass and the scan (8γ_{KP+2}·‖s‖·max‖t‖) is a valid starting
 // threshold: the probe rows above v* reach the list (their chunks' bound is >= their score), so the
 // final kt-th approximate score is >= thr0.  Features (TOPK_SF floats): s_P (fp64 dots with the

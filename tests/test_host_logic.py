@@ -48,6 +48,37 @@ def test_host_eigh_matches_numpy():
         assert np.allclose(V.T @ V, np.eye(n), atol=1e-12)
 
 
+@pytest.mark.parametrize("n", [1, 2, 50])
+def test_host_eigh_refuses_a_non_finite_matrix(n):
+    """A Gram with Inf or NaN entries (top-k over factors whose squared norms overflow the Gram's fp32
+    partial sums) is an error, not a walk of the QL iteration past the end of its arrays: w and V sit
+    in front of guard elements, which must survive; a matrix near the fp64 limit may fail or succeed,
+    within its arrays either way."""
+    L, lib = _lib()
+    rng = np.random.default_rng(n)
+    M = rng.standard_normal((n + 5, n))
+    base = M.T @ M
+    for what in ("inf", "nan", "all_inf", "near_max"):
+        A = base.copy()
+        if what == "inf":
+            A[n // 2, n // 2] = np.inf
+        elif what == "nan":
+            A[0, n - 1] = A[n - 1, 0] = np.nan
+        elif what == "all_inf":
+            A[:] = np.inf
+        else:
+            A *= 1e308 / np.abs(A).max()
+        A = np.ascontiguousarray(A)
+        wbuf = np.full(n + 1, 7.0)
+        Vbuf = np.full((n + 1, n), 7.0)
+        rc = lib.als_host_eigh(n, L.ptr(A, C.c_double), L.ptr(wbuf, C.c_double), L.ptr(Vbuf, C.c_double))
+        assert wbuf[n] == 7.0 and np.all(Vbuf[n] == 7.0), (what, "wrote past the end of w / V")
+        if what != "near_max":
+            assert rc == L.ALS_E_NOT_POSITIVE_DEFINITE, (what, rc)
+            with pytest.raises(L.ALSError):
+                L.check(rc)
+
+
 def test_spark_init_cpp_matches_oracle_bitwise():
     from oracle import spark_als as O
     L, lib = _lib()

@@ -344,3 +344,102 @@ def test_assert_rows_names_the_failing_row(tmp_path):
     got[5, 3] = np.nan
     with pytest.raises(AssertionError, match=f"id {ids[5]} "):
         LD.assert_rows(got, ref, ids, deg, paths, 1e-4, "nan", tmp_path)
+
+
+# ---- the top-k edge cases (tests/topk_cases.py) --------------------------------------------------
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _normal_or_zero(a):
+    a = np.abs(np.asarray(a, np.float32))
+    return bool(np.all(np.isfinite(a)) and not np.any((a != 0) & (a < np.finfo(np.float32).tiny)))
+
+
+@pytest.mark.parametrize("rank", [1, 2, 3, 4, 5, 50, 100, 200])
+def test_topk_edge_case_preconditions(rank):
+    """What each generator of tests/topk_cases.py promises, asserted with the oracle alone, so that a
+    failure of tests/test_gpu_topk_edges.py is about the kernel and not about its inputs."""
+    from tests import topk_cases as TC
+    CH = TC.chunk_rows(rank)
+    for gen, args in (("negative", (rank,)), ("mass_tie", (rank,)), ("zeros", (rank,)), ("group_ties", (rank, 4))):
+        uid, _, iid, _ = TC.case(gen, *args)
+        for ids in (uid, iid):  # sparse, shuffled, partly negative, distinct
+            assert np.unique(ids).size == ids.size and ids.min() < 0 < ids.max()
+            assert np.any(np.diff(ids) < 0) and np.ptp(ids.astype(np.int64)) > 4 * ids.size
+    # negative: every listed score below 0, and the last chunk is padded
+    uid, uf, iid, itf = TC.case("negative", rank)
+    assert iid.size > TC.TOPK_KC and iid.size % CH != 0 and uid.size == 77
+    _, ids, sc = TC.oracle_lists("negative", (rank,), 64)
+    assert np.all(ids >= iid.min()) and np.all(sc < 0)
+    # mass_tie: the list is the k smallest ids of the 300 identical rows, one score throughout
+    uid, uf, iid, itf = TC.case("mass_tie", rank)
+    tied = TC.mass_tie_ids(iid, itf)
+    assert tied.size == 300 > TC.TOPK_CAP
+    for k in (30, 64):
+        _, ids, sc = TC.oracle_lists("mass_tie", (rank,), k)
+        assert np.array_equal(ids, np.broadcast_to(tied[:k], ids.shape))
+        assert np.array_equal(_bits(sc[:, 0]), _bits(sc[:, k - 1]))
+    # group_ties: the k-th and the (k+1)-th score are one value for every src row
+    for k, copies in TC.GROUP_TIES.items():
+        _, ids, sc = TC.oracle_lists("group_ties", (rank, copies), k + 1)
+        assert np.array_equal(_bits(sc[:, k - 1]), _bits(sc[:, k])), (k, copies)
+        assert np.all(ids[:, k - 1] < ids[:, k])
+    # zeros: all-zero lists, k-th scores of exactly 0, and +0.0 only (F2J's sum starts from +0.0)
+    uid, uf, iid, itf = TC.case("zeros", rank)
+    assert 0.3 < np.mean(~itf.any(axis=1)) < 0.5 and np.sum(~uf.any(axis=1)) >= 10
+    for k in (30, 64):
+        for swap in (False, True):
+            _, ids, sc = TC.oracle_lists("zeros", (rank,), k, swap)
+            assert not np.any(_bits(sc) == 0x80000000), (k, swap)
+            if not swap:
+                assert np.sum(np.all(sc == 0, axis=1)) >= 10, k
+                assert np.mean(sc[:, k - 1] == 0) >= 0.2, (k, float(np.mean(sc[:, k - 1] == 0)))
+    if rank < 50:
+        return
+    # dynamic_range: no product and no score is subnormal or overflows, so the case says nothing
+    # about subnormal handling
+    for kind in TC.DYNAMIC_KINDS:
+        uid, uf, iid, itf = TC.case("dynamic_range", rank, kind)
+        assert TC.products_are_normal(uf, itf), kind
+        assert _normal_or_zero(O.f2j_sdot(uf[:, None, :], itf[None, :, :])), kind
+        nrm = np.linalg.norm(itf.astype(np.float64), axis=1)
+        if kind == "dst_spread":
+            assert nrm.max() / np.median(nrm) > 1e4 and nrm.max() / nrm.min() > 1e7
+        if kind == "src_spread":
+            snrm = np.linalg.norm(uf.astype(np.float64), axis=1)
+            assert snrm.max() / snrm.min() > 1e6
+        if kind == "dst_tiny":  # 13 - ceil(log2 max norm) is above pow2_scale's upper clamp of 60
+            assert 13 - np.frexp(nrm.max())[1] > 60
+        if kind == "dst_huge":
+            assert np.frexp(nrm.max())[1] > 60
+    # anisotropic: half of the src rows on the negative side of the leading direction
+    uid, uf, iid, itf = TC.case("anisotropic", rank)
+    w, V = np.linalg.eigh(itf.astype(np.float64).T @ itf.astype(np.float64))
+    lead = uf.astype(np.float64) @ V[:, -1]
+    assert 0.4 < np.mean(lead < 0) < 0.6 and w[-1] > 5 * w[-3]
+    # the size grid holds every boundary once
+    grid = TC.size_grid(rank)
+    assert set(TC.size_n_dst(rank)) | {100, 1000} == set(grid) and len(TC.size_n_dst(rank)) == 13
+    assert {1, 2, 63, 64, 65, CH - 1, CH, CH + 1, 511, 512, 513, 16 * CH - 1, 16 * CH + 1} <= set(grid)
+    assert all((67, k) in grid[n] for n in TC.size_n_dst(rank) for k in (1, 30, 64))
+    assert all((n, 30) in grid[16 * CH + 1] for n in TC.SIZE_N_SRC) and len(TC.SIZE_N_SRC) == 13
+    assert all((67, k) in grid[1000] for k in TC.SIZE_K_AT_1000) and len(TC.SIZE_K_AT_1000) == 13
+    assert all((67, k) in grid[100] for k in TC.SIZE_K_AT_100)
+
+
+@pytest.mark.parametrize("rank", [3, 50])
+def test_topk_edge_case_lists_two_restatements(rank):
+    """The expected lists of the tie, zero-row and negative-score cases from the numpy oracle and from
+    the C restatement: ids and score bits equal."""
+    from tests import topk_cases as TC
+    for gen in ("mass_tie", "zeros", "negative"):
+        uid, uf, iid, itf = TC.case(gen, rank)
+        for k in (30, 64):
+            src, ids, sc = TC.oracle_lists(gen, (rank,), k)
+            order = np.argsort(uid, kind="stable")
+            assert np.array_equal(src, uid[order])
+            cid, csc = cbind.recommend(uf[order], iid, itf, k, threads=4)
+            assert np.array_equal(ids, cid), (gen, k)
+            assert np.array_equal(_bits(sc), _bits(csc)), (gen, k)
