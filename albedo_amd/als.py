@@ -386,7 +386,7 @@ class ALSModel(_Params):
         import pandas as pd
         recs = []
         for r in range(len(src)):
-            m = ids[r] >= 0
+            m = ~np.isnan(sc[r])  # padding is told by the NaN score: -1 is a valid raw id
             recs.append([(int(i), float(s)) for i, s in zip(ids[r][m], sc[r][m])])
         keep = [i for i in range(len(src)) if recs[i]]
         return pd.DataFrame({src_col: src[keep], "recommendations": [recs[i] for i in keep]})

@@ -2351,7 +2351,12 @@ int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, con
   TRYC(topk_plan(c, ALS_USER, k, P));
   const int64_t per_rank = (nr + c->world - 1) / c->world;
   const int64_t lo = std::min<int64_t>(nr, (int64_t)c->rank * per_rank), hi = std::min<int64_t>(nr, lo + per_rank);
-  const int64_t chunk = topk_pass_rows(c);  // one pass for any realistic user count (see als_recommend)
+  // one pass for any realistic user count (see als_recommend); ALBEDO_TOPK_PASS (test knob): rows per pass
+  const int64_t chunk = [&] {
+    const char* e = std::getenv("ALBEDO_TOPK_PASS");
+    if (e && *e) return std::max<int64_t>(1 << 16, std::atoll(e));
+    return topk_pass_rows(c);
+  }();
   DevBuf d_oid, d_osc;
   TRYC(topk_begin(c, P, nr, (hi - lo + chunk - 1) / chunk, rows.data()));
   for (int64_t q0 = lo; q0 < hi; q0 += chunk) {
@@ -2360,7 +2365,7 @@ int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, con
     HIPCHK(d_osc.ensure(nc * k * 4));
     TRYC(topk_run_rows(c, P, rows.data() + q0, 0, q0, nc, d_oid.as<int32_t>(), d_osc.as<float>()));
     HIPCHK(eval_ndcg(d_oid.as<int32_t>(), d_act.as<int32_t>() + q0 * k, d_actn.as<int32_t>() + q0, nc, k,
-                     d_gain.as<double>(), d_vals.as<double>() + q0, st));
+                     c->s[ALS_ITEM].n, d_gain.as<double>(), d_vals.as<double>() + q0, st));
   }
   TRYC(topk_finish(c, P));
   std::vector<double> vals((size_t)std::max<int64_t>(per_rank, 1) * c->world, 0.0);

@@ -7,7 +7,8 @@
 //            (key desc, item asc) order (the deterministic collect_list order the host evaluator
 //            imposes): one wave per user selects them with a wave bitonic sort.
 //  predicted intoUserPredictedItems (:131-139) of the top-k lists (score desc, id asc): the lists
-//            als_recommend produces, kept on the device.
+//            als_recommend produces, kept on the device.  A list holds min(k, catalogue) raw ids of
+//            any sign (Spark ids are any Int); its padding is told by position, never by the id.
 //  ndcgAt    per user n = min(max(|pred|, |labSet|), k), dcg = Σ_{i<n} [pred_i ∈ lab] g_i,
 //            maxDcg = Σ_{i<min(n,|labSet|)} g_i (|labSet| = distinct items of the actual list),
 //            g_i = 1 / ln(i + 2) from the host's libm (the same
@@ -111,23 +112,23 @@ __global__ __launch_bounds__(256) void ev_actual_kernel(const uint32_t* __restri
 
 // one wave per evaluated user: ndcgAt(k) of the predicted list against the actual list
 __global__ __launch_bounds__(256) void ev_ndcg_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ act,
-                                                     const int32_t* __restrict__ act_n, int64_t n_users, int k,
+                                                     const int32_t* __restrict__ act_n, int64_t n_users, int k, int np,
                                                      const double* __restrict__ gain, double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (u >= n_users) return;
-  const int32_t p = lane < k ? pred[u * k + lane] : -1;
+  // np = min(k, catalogue): the lists of known users are dense, the tail past np is padding
+  const int32_t p = lane < np ? pred[u * k + lane] : -1;
   const int nl = act_n[u];
   const int32_t lab = lane < nl ? act[u * k + lane] : -1;
   bool hit = false, dup = false;
   for (int j = 0; j < nl; ++j) {
     const int32_t v = __shfl(lab, j);
-    hit |= (p >= 0 && p == v);
+    hit |= (lane < np && p == v);  // -1 is a valid raw id: only the position tells padding
     dup |= (j < lane && v == lab);  // an earlier entry holds the same item
   }
   // |labSet|: mllib takes the size of the label SET (a user's duplicated (user, item) rows count once)
   const int ns = __popcll(__ballot(lane < nl && !dup));
-  const int np = __popcll(__ballot(lane < k && p >= 0));  // the lists are dense: -1 only at the tail
   const uint64_t hits = __ballot(hit);
   if (lane == 0) {
     double v = 0.0;
@@ -193,12 +194,14 @@ hipError_t eval_actual_lists(const uint32_t* idx_sorted, const int64_t* offsets,
 }
 
 hipError_t eval_ndcg(const int32_t* pred, const int32_t* act, const int32_t* act_n, int64_t n_users, int k,
-                     const double* gain, double* out, hipStream_t s) {
+                     int64_t n_dst, const double* gain, double* out, hipStream_t s) {
   if (n_users <= 0) return hipSuccess;
-  if (k < 1 || k > 64) return hipErrorInvalidValue;
+  if (k < 1 || k > 64 || n_dst < 0) return hipErrorInvalidValue;
+  const int np = (int)std::min<int64_t>(k, n_dst);
   for (int64_t u0 = 0; u0 < n_users; u0 += max_rows_per_launch(64)) {
     const int64_t nu = std::min<int64_t>(n_users - u0, max_rows_per_launch(64));
-    ev_ndcg_kernel<<<(int)((nu + 3) / 4), 256, 0, s>>>(pred + u0 * k, act + u0 * k, act_n + u0, nu, k, gain, out + u0);
+    ev_ndcg_kernel<<<(int)((nu + 3) / 4), 256, 0, s>>>(pred + u0 * k, act + u0 * k, act_n + u0, nu, k, np, gain,
+                                                       out + u0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

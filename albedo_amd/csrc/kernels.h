@@ -241,9 +241,10 @@ hipError_t eval_group_users(const int32_t* user, int64_t n, const int32_t* ids, 
 hipError_t eval_actual_lists(const uint32_t* idx_sorted, const int64_t* offsets, const int32_t* counts, int64_t n_runs,
                              const int64_t* key, const int32_t* item, int k, int32_t* act, int32_t* act_n,
                              hipStream_t s);
-// ndcgAt(k) per user of pred [n][k] (raw ids, -1 tail) against act; gain[i] = 1 / ln(i + 2)
+// ndcgAt(k) per user of pred [n][k] (raw ids of any sign; the first min(k, n_dst) entries are the list,
+// the rest padding) against act; gain[i] = 1 / ln(i + 2)
 hipError_t eval_ndcg(const int32_t* pred, const int32_t* act, const int32_t* act_n, int64_t n_users, int k,
-                     const double* gain, double* out, hipStream_t s);
+                     int64_t n_dst, const double* gain, double* out, hipStream_t s);
 // *out = bits of max_r ||T[r][0..kreal)||_2 computed in fp64
 hipError_t launch_rownorm_max(const float* T, int64_t n, int KP, int kreal, unsigned long long* out, hipStream_t s);
 

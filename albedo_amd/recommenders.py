@@ -118,7 +118,7 @@ class ALSRecommender(Recommender):
         if active.size == 0 or num <= 0:
             return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.float32)
         src, ids, sc = model.recommend_np(num, subset=active)
-        keep = ids >= 0
+        keep = ~np.isnan(sc)  # padding is told by the NaN score: -1 is a valid raw id
         return np.repeat(src, keep.sum(axis=1)), ids[keep], sc[keep]
 
     def recommendForUsers(self, userDF):

@@ -146,6 +146,8 @@ int als_model_create(int32_t rank, int64_t n_users, const int32_t* user_ids, con
  * for each requested src id (all src rows when subset==NULL, ascending) the top-k dst ids by the
  * F2J-order fp32 dot product (ALSRecommender.scala:51), sorted (score desc, id asc).
  * Outputs [n_src][k]; rows with fewer than k dst entries are padded with id -1 / score NaN.
+ * -1 is also a valid raw id (ids are any int32): the NaN score is the padding marker, and a list is
+ * dense (its min(k, n_dst) entries come first).
  * Unknown subset ids produce an all-padding row.  src_ids_out may be NULL.
  * k <= 64: MFMA pre-selection + exact rescoring; 64 < k <= 512: exact full scan per src row (slower);
  * k > 512: ALS_E_UNSUPPORTED. */

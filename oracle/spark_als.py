@@ -457,11 +457,21 @@ def ndcg_at(pairs, k: int) -> float:
 
 def into_user_items(user, item, order_key, k):
     """intoUserActualItems / intoUserPredictedItems: rank() over (user ORDER BY key desc) <= k,
-    collect_list; the list order is made deterministic as (key desc, item asc)."""
+    collect_list; the list order is made deterministic as (key desc, item asc).
+
+    Integer keys (starred_at in microseconds is an int64) are ordered exactly: the descending order
+    is the ascending order of ~key, which has no overflow at INT64_MIN (-key has) and, unlike a cast
+    to float64, keeps keys beyond 2^53 apart.  Any other key type is ordered as float64."""
     user = np.asarray(user)
     item = np.asarray(item)
-    key = np.asarray(order_key, dtype=np.float64)
-    order = np.lexsort((item, -key, user))
+    key = np.asarray(order_key)
+    if key.dtype.kind in "iub":
+        if key.dtype.kind == "u" and key.size and int(key.max()) > np.iinfo(np.int64).max:
+            raise ValueError("unsigned order keys above INT64_MAX")
+        key = ~key.astype(np.int64)  # ascending ~key = descending key
+    else:
+        key = -np.asarray(key, dtype=np.float64)
+    order = np.lexsort((item, key, user))
     out = {}
     u_s, i_s, k_s = user[order], item[order], key[order]
     start = 0
@@ -472,7 +482,7 @@ def into_user_items(user, item, order_key, k):
             end += 1
         keys = k_s[start:end]
         # rank() = 1 + number of strictly greater keys in the partition (ties share a rank)
-        ranks = 1 + np.searchsorted(-keys, -keys, side="left")
+        ranks = 1 + np.searchsorted(keys, keys, side="left")  # keys: the descending-order keys, ascending
         out[int(u_s[start])] = [int(x) for x in i_s[start:end][ranks <= k]]
         start = end
     return out

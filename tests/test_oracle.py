@@ -443,3 +443,235 @@ def test_topk_edge_case_lists_two_restatements(rank):
             cid, csc = cbind.recommend(uf[order], iid, itf, k, threads=4)
             assert np.array_equal(ids, cid), (gen, k)
             assert np.array_equal(_bits(sc), _bits(csc)), (gen, k)
+
+
+# ---- the ingest edge cases (tests/ingest_cases.py) -----------------------------------------------
+
+def test_ingest_edge_case_preconditions():
+    """What the generators of tests/ingest_cases.py promise: the extreme ids survive the int32 cast on
+    both sides, the top-bit and bit-0 pairs differ in that bit alone, the duplicated pairs sit in rows
+    of every listed degree in both orientations with the listed copy counts and different ratings
+    (one pair +r / -r), the degenerate shapes and sizes are what their names say, and every COO
+    arrives shuffled."""
+    from tests import ingest_cases as IC
+    user, item, r = IC.case("extreme_ids")
+    assert user.dtype == item.dtype == np.int32 and r.dtype == np.float32
+    for ids in (user, item):
+        assert set(IC.EXTREME_IDS) <= set(ids.tolist()) and set(IC.special_ids()) <= set(ids.tolist())
+        assert np.unique(ids).size >= 128 and np.any(np.diff(ids.astype(np.int64)) < 0)
+    assert all((a ^ b) & 0xFFFFFFFF == 0x80000000 for a, b in IC.TOP_BIT_PAIRS)
+    assert all((a ^ b) == 1 for a, b in IC.BIT0_PAIRS) and np.all(r > 0)
+    B = O.make_blocks(user, item, r)
+    assert B.user_ids[0] == IC.I32_MIN and B.user_ids[-1] == IC.I32_MAX and np.all(np.diff(B.user_ids.astype(np.int64)) > 0)
+    assert B.item_ids[0] == IC.I32_MIN and B.item_ids[-1] == IC.I32_MAX
+
+    user, item, r = IC.case("duplicates")
+    B = O.make_blocks(user, item, r)
+    assert IC.dup_rows() == [(8, 2), (8, 3), (16, 2), (16, 3), (17, 2), (17, 3), (64, 2), (64, 3), (64, 64),
+                             (65, 2), (65, 3), (65, 64)]
+    for ids, ptr, col, val in ((B.user_ids, B.u_ptr, B.u_col, B.u_val), (B.item_ids, B.i_ptr, B.i_col, B.i_val)):
+        assert np.unique(ids).size >= 128  # the Gram of either side has full rank at rank 128
+        for d, c in IC.dup_rows():
+            j = int(np.searchsorted(ids, 700000 + 1000 * d + c))
+            assert ids[j] == 700000 + 1000 * d + c and ptr[j + 1] - ptr[j] == d, (d, c)
+            cols, cnt = np.unique(col[ptr[j]:ptr[j + 1]], return_counts=True)
+            assert sorted(cnt.tolist()) == [1] * (d - c) + [c], (d, c)
+            rr = val[ptr[j]:ptr[j + 1]][col[ptr[j]:ptr[j + 1]] == cols[np.argmax(cnt)]]
+            assert np.unique(rr).size == c, (d, c)
+            if c == 2:
+                assert sorted(rr.tolist()) == [-2.5, 2.5]
+    # the copies also land in ordinary rows of the other orientation, which then hold > 64 ratings
+    assert np.diff(B.u_ptr).max() >= 64 and np.diff(B.i_ptr).max() >= 64
+
+    assert IC.case("single")[0].size == 1
+    for name, nu, ni, n in (("one_user", 1, 300, 300), ("one_item", 300, 1, 300), ("one_user_repeats", 1, 40, 300)):
+        user, item, r = IC.case(name)
+        assert (np.unique(user).size, np.unique(item).size, user.size) == (nu, ni, n), name
+    for v in (255, 256, 257):
+        user, item, r = IC.case("square", v)
+        assert np.unique(user).size == np.unique(item).size == v and user.size == 4 * v
+    for n in (255, 256, 257):
+        assert IC.case("sized", n)[0].size == n
+    assert IC.N_PAST_CAP == 8192 * 256 + 257 and (255, 256, 257) == tuple(c[1][0] for c in IC.SMALL_CASES[-3:])
+    for c in IC.SMALL_CASES[:2] + IC.SMALL_CASES[3:]:
+        user, item, r = IC.case(*c[0:1], *c[1])
+        assert user.size == item.size == r.size
+        assert np.any(np.diff(user.astype(np.int64)) < 0) or np.any(np.diff(item.astype(np.int64)) < 0), c
+
+
+def test_ingest_past_cap_shape():
+    """The case past the grid-stride launch cap: 8192 * 256 + 257 ratings over a few thousand rows per side."""
+    from tests import ingest_cases as IC
+    user, item, r = IC.case("past_cap")
+    assert user.size == IC.N_PAST_CAP > IC.GRID_CAP
+    assert 2000 <= np.unique(user).size <= 4000 and 2000 <= np.unique(item).size <= 4000
+
+
+@pytest.mark.parametrize("k", [50, 128])
+def test_duplicates_case_exposes_a_merging_ingest(k):
+    """Duplicates enter the normal equation once per copy.  An ingest that merged the copies of a pair
+    into one summed rating would change b by (copies - 1)·y, lambda·n by reg·(copies - 1) and, for the
+    +r / -r pair, drop the pair altogether: on every row of the duplicates case that holds a
+    duplicated pair the oracle on the merged COO is more than 10x the GPU tolerance (1e-4) away from
+    the true one, on both halves; rows without a duplicate do not move on the item half."""
+    from tests import ingest_cases as IC
+    from tests import ladder as LD
+    user, item, r = IC.case("duplicates")
+    B = O.make_blocks(user, item, r)
+    Bm = O.make_blocks(*IC.merge_duplicates(user, item, r))
+    assert np.array_equal(B.user_ids, Bm.user_ids) and np.array_equal(B.item_ids, Bm.item_ids)
+    assert len(Bm.u_col) < len(B.u_col)
+    kw = dict(reg=0.5, alpha=10.0, implicit=True)
+    U = LD.unit_rows(np.random.default_rng(k), len(B.user_ids), k)
+    V = O.half_sweep(U, B.i_ptr, B.i_col, B.i_val, **kw)
+    Vm = O.half_sweep(U, Bm.i_ptr, Bm.i_col, Bm.i_val, **kw)
+    X = O.half_sweep(V, B.u_ptr, B.u_col, B.u_val, **kw)
+    Xm = O.half_sweep(V, Bm.u_ptr, Bm.u_col, Bm.u_val, **kw)
+    for name, a, b, deg, degm in (("item", V, Vm, np.diff(B.i_ptr), np.diff(Bm.i_ptr)),
+                                  ("user", X, Xm, np.diff(B.u_ptr), np.diff(Bm.u_ptr))):
+        err = LD.row_errors(b, a)
+        has_dup = deg != degm
+        assert has_dup.sum() >= len(IC.dup_rows()), name
+        assert err[has_dup].min() > 10 * 1e-4, (name, float(err[has_dup].min()))
+        assert err[~has_dup].max() == 0.0, name
+
+
+# ---- the NDCG edge cases (tests/eval_cases.py) ----------------------------------------------------
+
+def _into_user_items_float64(user, item, order_key, k):
+    """O.into_user_items as it was before it ordered integer keys exactly (keys cast to float64)."""
+    user, item = np.asarray(user), np.asarray(item)
+    key = np.asarray(order_key, dtype=np.float64)
+    order = np.lexsort((item, -key, user))
+    u_s, i_s, k_s = user[order], item[order], key[order]
+    out = {}
+    start = np.r_[0, 1 + np.nonzero(u_s[1:] != u_s[:-1])[0]]
+    for a, b in zip(start, np.r_[start[1:], u_s.size]):
+        ranks = 1 + np.searchsorted(-k_s[a:b], -k_s[a:b], side="left")
+        out[int(u_s[a])] = [int(x) for x in i_s[a:b][ranks <= k]]
+    return out
+
+
+@pytest.mark.parametrize("k", [30, 10])
+def test_into_user_items_integer_keys_exact_and_unchanged(k):
+    """The integer-exact O.into_user_items returns the lists the float64 version returned on the input
+    of test_device_ndcg_matches_oracle (timestamps far below 2^53) and on float keys; it keeps keys
+    apart that differ by 1 above 2^53, and orders INT64_MIN (whose negation overflows) last."""
+    from albedo_amd.synthetic import SynthSpec, generate
+    d = generate(SynthSpec(2500, 600, 40000, seed=19), with_timestamps=True)
+    rng = np.random.default_rng(k)
+    ts = d["ts"] // 1_000_000
+    dup = rng.choice(d["user"].size, 400, replace=False)
+    users = np.r_[d["user"], d["user"][dup], np.full(5, 123456789, np.int32)]
+    items = np.r_[d["item"], d["item"][dup], d["item"][:5]]
+    keys = np.r_[ts, ts[dup] + 1 + rng.integers(0, 3, dup.size), ts[:5]]
+    assert keys.dtype == np.int64 and np.abs(keys).max() < 2 ** 53
+    old = _into_user_items_float64(users, items, keys, k)
+    assert O.into_user_items(users, items, keys, k) == old
+    assert O.into_user_items(users, items, keys.astype(np.float64), k) == old
+    assert O.into_user_items(users, items, keys.astype(np.int32) if np.abs(keys).max() < 2 ** 31 else keys, k) == old
+    big = 1 << 60
+    ky = np.array([big, big + 1, -(1 << 63), (1 << 63) - 1, -5], np.int64)
+    it = np.array([1, 2, 0, 9, 3])
+    assert O.into_user_items(np.zeros(5, np.int32), it, ky, 5) == {0: [9, 2, 1, 3, 0]}
+    assert O.into_user_items(np.zeros(5, np.int32), it, ky, 2) == {0: [9, 2]}
+    assert _into_user_items_float64(np.zeros(5, np.int32), it, ky, 2)[0][1] == 1  # the float order: a tie
+
+
+def test_eval_edge_case_preconditions():
+    """What the generators of tests/eval_cases.py promise, asserted with the oracle alone."""
+    from tests import eval_cases as EC
+    k = 30
+    for variant in EC.LENGTH_VARIANTS:
+        m, (users, items, keys) = EC.case("lengths", variant)
+        who, cnt = np.unique(users, return_counts=True)
+        assert sorted(cnt.tolist()) == EC.LENGTHS and np.all(np.isin(who, m[0]))  # every length is present
+        assert {1, 29, 30, 31, 63, 64, 65, 127, 128, 129, 200, 1000} == set(cnt.tolist())
+        assert np.any(np.diff(users) < 0)
+        for u in who:
+            ky = keys[users == u]  # the user's rows in input order
+            if variant == "ties":
+                assert np.all(ky == ky[0])
+            if variant == "last64":
+                assert np.unique(ky).size == ky.size
+                assert np.sort(ky)[-k:][0] <= np.min(np.sort(ky[-64:])[-k:]), u  # the top k are among the last 64 rows
+                if ky.size > 128:
+                    assert np.max(ky[:-64]) < np.sort(ky)[-k:][0]
+        if variant == "random":
+            assert any(np.unique(keys[users == u]).size < np.sum(users == u) for u in who)
+    # keys: the 2^53 pairs are two int64 keys and one float64, and they decide the k-th place
+    m, (users, items, keys) = EC.case("keys")
+    assert np.int64(EC.BIG) != np.int64(EC.BIG + 1) and float(EC.BIG) == float(EC.BIG + 1) and EC.BIG > 2 ** 53
+    exact, lossy = O.into_user_items(users, items, keys, k), _into_user_items_float64(users, items, keys, k)
+    swapped = [u for u in exact if exact[u][:k] != lossy[u][:k]]
+    assert len(swapped) >= 40 and all(np.sum((users == u) & (keys >= EC.BIG)) == k + 1 for u in m[0][:40])
+    assert {EC.I64_MIN, EC.I64_MAX, -1, 0} <= set(keys.tolist()) and np.sum(keys < 0) > 100
+    _, ref_exact, _ = EC.reference("keys", (), k)
+    known, pred = EC.predicted_lists(m, users, k)
+    ref_lossy = np.array([O.ndcg_at([(pred[int(u)], lossy[int(u)][:k])], k) for u in known])
+    assert np.sum(ref_exact != ref_lossy) >= 3  # a float64 order of the keys changes per-user values
+    # item id extremes: catalogues of either sign, the special ids, lists shorter than k
+    neg, mix, ext = (EC.case("bag", c)[0][2] for c in ("negative", "mixed", "extreme"))
+    assert neg.max() < 0 and mix.min() < 0 < mix.max() and {-1, EC.I32_MIN, EC.I32_MAX} <= set(ext.tolist())
+    assert EC.case("bag", "five")[0][2].size == 5 and EC.case("bag", "twentynine")[0][2].size == 29
+    for kind in EC.CATALOGUES:
+        m, (users, items, keys) = EC.case("bag", kind)
+        roles = EC.bag_roles()
+        actual = O.into_user_items(users, items, keys, k)
+        known, vals, mean = EC.reference("bag", (kind,), k)
+        val = dict(zip(known.tolist(), vals.tolist()))
+        assert set(known.tolist()) == set(sum((roles[r] for r in roles if r != "unknown_users"), []))
+        assert not np.isin(roles["unknown_users"], m[0]).any() and np.isin(roles["unknown_users"], users).all()
+        assert min(roles["unknown_users"]) < m[0].min() and max(roles["unknown_users"]) > m[0].max()
+        assert all(not np.isin(actual[u], m[2]).any() and val[u] == 0.0 for u in roles["unknown_items"])
+        assert all(len(set(actual[u])) == 1 for u in roles["one_item"])
+        assert any(len(actual[u]) > 1 for u in roles["one_item"])
+        sent = (items == EC.I32_MAX) & (keys == EC.I64_MIN)
+        assert all(np.sum(sent & (users == u)) >= 1 for u in roles["sentinel"])
+        # hits exist, so a kernel that never credits a hit on this catalogue is caught
+        assert np.sum(vals > 0) >= 10 and 0 < mean < 1, (kind, int(np.sum(vals > 0)))
+        if kind in ("five", "twentynine"):  # n is decided by |labSet| for some users
+            known, pred = EC.predicted_lists(m, users, k)
+            assert all(len(p) == m[2].size < k for p in pred.values())
+            assert any(len(set(actual[int(u)][:k])) > m[2].size for u in known)
+    # with hits only at negative ids, dropping them changes the value of most users
+    m, (users, items, keys) = EC.case("bag", "negative")
+    known, pred = EC.predicted_lists(m, users, k)
+    assert all(x < 0 for p in pred.values() for x in p)
+    # join edges
+    m, (users, items, keys) = EC.case("only_unknown_users")
+    assert users.size > 0 and not np.isin(users, m[0]).any()
+    known, vals, mean = EC.reference("only_unknown_users", (), k)
+    assert known.size == 0 and np.isnan(mean)
+    m, (users, items, keys) = EC.case("bag", "mixed", 1)
+    assert m[0].size == 1 and EC.reference("bag", ("mixed", 1), k)[0].tolist() == [10]
+    assert np.unique(users).size == 7
+
+
+def test_actual_lists_two_restatements():
+    """tests/eval_cases.py actual_lists (one lexsort, first k of each group) equals
+    O.into_user_items(...)[:k] on every small case at k = 1, 2, 30, 63, 64."""
+    from tests import eval_cases as EC
+    for c in EC.SMALL_CASES:
+        _, (users, items, keys) = EC.case(c[0], *c[1])
+        for k in (1, 2, 30, 63, 64):
+            a = EC.actual_lists(users, items, keys, k)
+            b = {u: v[:k] for u, v in O.into_user_items(users, items, keys, k).items()}
+            assert a == b, (c, k)
+
+
+def test_eval_large_case_shapes():
+    """The case past ev_map_rows_kernel's launch cap and the three-pass case."""
+    from tests import eval_cases as EC
+    m, (users, items, keys) = EC.case("past_cap")
+    assert users.size == EC.N_PAST_CAP == 16384 * 256 + 257
+    who = np.unique(users)
+    assert np.isin(who, m[0]).sum() == 36 and (~np.isin(who, m[0])).sum() == 3
+    m, (users, items, keys) = EC.case("passes")
+    lm, (lu, li, lk) = EC.case("lengths", "random")
+    known = np.intersect1d(np.unique(users), m[0])
+    assert known.size == EC.PASS_USERS + 12 > 2 * EC.PASS_ROWS and np.isin(lm[0][:12], known).all()
+    at = np.searchsorted(known, np.sort(lm[0][:12])) // EC.PASS_ROWS  # the pass of each user of lengths
+    assert at.tolist() == [0] * 6 + [1] * 6 and (known.size - 1) // EC.PASS_ROWS == 2
+    for u in lm[0][:12]:
+        assert np.array_equal(np.sort(keys[users == u]), np.sort(lk[lu == u]))
