@@ -863,6 +863,7 @@ int heavy_launches(als_ctx* c, const Side& T, SolveArgs a, int64_t h0, int64_t h
     else HIPCHK(launch_solve_heavy(KP, b, c->st));
   }
   a.rows = rows + h0 + ns;
+  a.desc = T.d_desc.as<int32_t>() + 4 * (h0 + ns);  // the descriptors follow d_rows entry by entry
   a.n_rows = hn - ns;
   a.prebuilt = nullptr;
   if (nnls) HIPCHK(launch_solve_nnls(KP, a, c->d_Gt.as<float>(), c->st));

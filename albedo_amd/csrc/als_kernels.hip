@@ -659,11 +659,20 @@ constexpr int light_occupancy() {
   return D > 64 ? 2 : (D == 16 && KP <= 128) ? 6 : (KP == 128 && D == 32) ? 3 : (KP <= 128) ? 4 : 2;
 }
 
+// the split-fp16 S build (and its column-scale bound) serves D >= 64 and the register-resident rows
+template <int KP, int D>
+constexpr bool light_keepz() { return D <= 32 && D * KP <= 4096; }
+template <int KP, int D>
+constexpr bool light_split_s() { return D >= 64 || light_keepz<KP, D>(); }
+
 // One light row: j, degree d (wave-uniform), lane e < d holds rating r and src row colE of entry e;
-// D > 64: lane e also holds entry 64 + e (r2, colE2).
+// D > 64: lane e also holds entry 64 + e (r2, colE2).  lamv[h] / icsv[h]: a.lam and the inverse column
+// scale a.colscale[KP + .] of column lane + 64h, loaded by the caller together with the row's entries
+// (they do not depend on the row, so they never cost a round trip of their own).
 template <int KP, int D>
 __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, float r, int colE, float r2, int colE2,
-                                          float* smem, int wave) {
+                                          const float (&lamv)[KP / 64], const float (&icsv)[KP / 64], float* smem,
+                                          int wave) {
   constexpr int NB = D / 16, NT = NB * (NB + 1) / 2, TRI = light_wave_lds(D), NHC = KP / 64;
   constexpr bool TWO = D > 64;  // two entries per lane
   const int lane = threadIdx.x & 63, g = lane >> 4, i16 = lane & 15;
@@ -685,13 +694,34 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
     vB[I] = __shfl((int)(I < 4 ? valid : valid2), 16 * (I & 3) + i16) != 0;
   }
   constexpr int NC = KP / 16;
-  constexpr bool KEEPZ = D <= 32 && D * KP <= 4096;  // keep the gathered rows in registers for x' (D = 64 at KP = 128, 2 waves per SIMD: measured slower)
+  constexpr bool KEEPZ = light_keepz<KP, D>();  // keep the gathered rows in registers for x' (D = 64 at KP = 128, 2 waves per SIMD: measured slower)
   f32x4 zf[KEEPZ ? NB : 1][KEEPZ ? NC : 1];
   if constexpr (KEEPZ) {  // issue every gather up front: one latency for the whole row
 #pragma unroll
     for (int I = 0; I < NB; ++I)
 #pragma unroll
       for (int c = 0; c < NC; ++c) zf[I][c] = vB[I] ? ld4(a.Z + (int64_t)colB[I] * KP + 16 * c + 4 * g) : zero4();
+  }
+  // D >= 64 re-gathers the rows per 32-column step of the S build, and no gather is conditional: a
+  // lane whose entry is past the row end or masked (c = 0) gathers the zero row of Z (a.zero_row, as
+  // light16.hip does), which gives exactly the zeros the skipped load used to stand for, so all 2·NB
+  // loads of a step are in flight before the first wait.  Step 0 goes out here, ahead of the D^-1/2
+  // fill.  Look-ahead: the registers of blocks I < NB - LATE are refilled with step q + 1 as soon as
+  // step q's values are converted, so those loads fly behind step q's MFMAs; the last LATE blocks are
+  // loaded at the start of their own step, behind the converts of the others.  KP = 128, D = 64 runs
+  // at 4 workgroups per CU (128 VGPRs): LATE = 0 needs 128 + 28 B of scratch, LATE = 2 127 and none,
+  // no look-ahead at all 113 (and measured 1.3 % slower than LATE = 2); the other instances fit LATE = 0.
+  constexpr bool PUSHG = !KEEPZ && D >= 64;
+  constexpr int LATE = (KP == 128 && D == 64) ? 2 : 0;
+  f32x4 zr0[PUSHG ? NB : 1], zr1[PUSHG ? NB : 1];
+  const float* zpB[PUSHG ? NB : 1];
+  if constexpr (PUSHG) {
+#pragma unroll
+    for (int I = 0; I < NB; ++I) {
+      zpB[I] = a.Z + (vB[I] ? (int64_t)colB[I] : a.zero_row) * KP + 8 * g;
+      zr0[I] = ld4(zpB[I]);
+      zr1[I] = ld4(zpB[I] + 4);
+    }
   }
   f32x4 acc[NT];
 #pragma unroll
@@ -702,12 +732,12 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
 #pragma unroll
   for (int h = 0; h < NHC; ++h) {
     const int cc = lane + 64 * h;
-    const float dd = a.lam[cc] + lamn;
+    const float dd = lamv[h] + lamn;
     if (cc < a.kreal && !(dd > 0.f)) bad = true;
     sdl[cc] = (cc < a.kreal && dd > 0.f) ? frsq(dd) : 0.f;
   }
   WAVE_LDS_SYNC();
-  if constexpr (D >= 64 || KEEPZ) {
+  if constexpr (light_split_s<KP, D>()) {
     // S on split-fp16 MFMA (hi·hi + hi·lo + lo·hi, 32 columns per instruction: at D = 64 120 instead
     // of 320 fp32 MFMAs, at D = 16 12 x 16 cycles instead of 32 x 32).  One power-of-two scale for the
     // whole row (so S unscales exactly): |Z[.][c]| < 2^(13 - e_c) (colscale), hence
@@ -718,7 +748,7 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
 #pragma unroll
     for (int h = 0; h < NHC; ++h) {
       const int cc = lane + 64 * h;
-      bnd = fmaxf(bnd, sdl[cc] * a.colscale[KP + cc]);
+      bnd = fmaxf(bnd, sdl[cc] * icsv[h]);
     }
     bnd = wave_max_dpp(bnd);
     int ex = 0;
@@ -727,6 +757,17 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
     constexpr int NQ = KP / 32;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
+      if constexpr (PUSHG) {
+        __builtin_amdgcn_sched_barrier(0);  // converts and refills, then the MFMAs
+        if (q > 0) {
+#pragma unroll
+          for (int I = NB - LATE; I < NB; ++I) {
+            zr0[I] = ld4(zpB[I] + 32 * q);
+            zr1[I] = ld4(zpB[I] + 32 * q + 4);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       const f32x4 s0 = KEEPZ ? ld4(sdl + 32 * q + 4 * g) : ld4(sdl + 32 * q + 8 * g);
       const f32x4 s1 = KEEPZ ? ld4(sdl + 32 * q + 16 + 4 * g) : ld4(sdl + 32 * q + 8 * g + 4);
       f16x8 zh[NB], zl[NB];
@@ -737,9 +778,8 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
           v0 = zf[I][2 * q];
           v1 = zf[I][2 * q + 1];
         } else {
-          const float* zp = a.Z + (int64_t)colB[I] * KP + 32 * q + 8 * g;
-          v0 = vB[I] ? ld4(zp) : zero4();
-          v1 = vB[I] ? ld4(zp + 4) : zero4();
+          v0 = zr0[I];
+          v1 = zr1[I];
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -749,7 +789,16 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
           zh[I][e] = hv;
           zl[I][e] = (_Float16)(v - (float)hv);
         }
+        if constexpr (PUSHG) {
+          if (q + 1 < NQ && I < NB - LATE) {
+            __builtin_amdgcn_sched_barrier(0);  // after this block's converts: its registers are free
+            zr0[I] = ld4(zpB[I] + 32 * (q + 1));
+            zr1[I] = ld4(zpB[I] + 32 * (q + 1) + 4);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
       }
+      if constexpr (PUSHG) __builtin_amdgcn_sched_barrier(0);
       static_for<0, NT>([&](auto t) {
         constexpr TilePair p = upper_tile(decltype(t)::value, NB);
         acc[t] = mfma_h(zh[p.a], zh[p.b], acc[t]);
@@ -891,32 +940,49 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
       }
     }
   } else {
-    // lanes own columns lane + 64h; gathers issued 8 entries at a time
-    float xacc[NHC];
-#pragma unroll
-    for (int h = 0; h < NHC; ++h) xacc[h] = 0.f;
-    for (int e0 = 0; e0 < d; e0 += 8) {
-      float ve[8], zz[8][NHC];
+    // lane l owns the NHC consecutive columns NHC·l ..: one load instruction per gathered row.  The
+    // gathers go 8 entries at a time, two batches deep: batch b + 1 is in flight behind batch b's FMAs.
+    // Entries past the row end are clamped to the last one with weight 0, so every load is
+    // unconditional (the batch issued behind the last one is never used); each column still sums its
+    // entries in ascending order.
+    typedef float xvec __attribute__((ext_vector_type(NHC)));
+    struct XBatch {
+      float ve[8];
+      xvec zz[8];
+    };
+    auto xload = [&](int e0, XBatch& b) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int e = e0 + u < d ? e0 + u : d - 1;  // wave-uniform
         const bool hi = TWO && e >= 64;
-        ve[u] = e0 + u < d ? rdlane(hi ? y2 : y, e & 63) : 0.f;
-        const float* zr = a.Z + (int64_t)rdlane_i(hi ? colE2 : colE, e & 63) * KP + lane;
-#pragma unroll
-        for (int h = 0; h < NHC; ++h) zz[u][h] = zr[64 * h];
+        b.ve[u] = e0 + u < d ? rdlane(hi ? y2 : y, e & 63) : 0.f;
+        const float* zr = a.Z + (int64_t)rdlane_i(hi ? colE2 : colE, e & 63) * KP + NHC * lane;
+        b.zz[u] = *reinterpret_cast<const xvec*>(zr);
       }
+    };
+    xvec xacc = 0.f;
+    auto xfma = [&](const XBatch& b) {
 #pragma unroll
       for (int u = 0; u < 8; ++u)
 #pragma unroll
-        for (int h = 0; h < NHC; ++h) xacc[h] = fmaf(ve[u], zz[u][h], xacc[h]);
+        for (int h = 0; h < NHC; ++h) xacc[h] = fmaf(b.ve[u], b.zz[u][h], xacc[h]);
+    };
+    XBatch ba, bb;
+    xload(0, ba);
+    for (int e0 = 0;;) {
+      xload(e0 + 8, bb);
+      xfma(ba);
+      e0 += 8;
+      if (e0 >= d) break;
+      xload(e0 + 8, ba);
+      xfma(bb);
+      e0 += 8;
+      if (e0 >= d) break;
     }
+    xvec sd;
 #pragma unroll
-    for (int h = 0; h < NHC; ++h) {
-      const int c = lane + 64 * h;
-      const float sd = sdl[c];
-      a.X[(int64_t)j * KP + c] = xacc[h] * (sd * sd);
-    }
+    for (int h = 0; h < NHC; ++h) sd[h] = sdl[NHC * lane + h];
+    *reinterpret_cast<xvec*>(a.X + (int64_t)j * KP + NHC * lane) = xacc * (sd * sd);
   }
 }
 
@@ -930,6 +996,13 @@ __global__ __launch_bounds__(256, (light_occupancy<KP, D>())) void solve_light_k
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t ridx = (int64_t)blockIdx.x * 4 + wave;
   if (ridx >= a.n_rows) return;  // wave-uniform; this kernel has no workgroup barrier
+  // the row-independent loads go out first: one wait covers them and the row's entries
+  float lamv[KP / 64], icsv[KP / 64];
+#pragma unroll
+  for (int h = 0; h < KP / 64; ++h) {
+    lamv[h] = a.lam[lane + 64 * h];
+    icsv[h] = light_split_s<KP, D>() ? a.colscale[KP + lane + 64 * h] : 0.f;
+  }
   typedef __attribute__((address_space(4))) const int cint;
   cint* q = (cint*)(a.desc) + 4 * ridx;  // constant address space: s_load_dwordx4
   const int j = q[0], d = q[3];
@@ -944,7 +1017,7 @@ __global__ __launch_bounds__(256, (light_occupancy<KP, D>())) void solve_light_k
     r2 = a.val[p0 + 64 + lane];
     colE2 = a.col[p0 + 64 + lane];
   }
-  light_row<KP, D>(a, j, d, r, colE, r2, colE2, smem, wave);
+  light_row<KP, D>(a, j, d, r, colE, r2, colE2, lamv, icsv, smem, wave);
 }
 
 hipError_t launch_solve_light(int KP, int D, const SolveArgs& a0, hipStream_t s) {

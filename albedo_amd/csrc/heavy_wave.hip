@@ -76,13 +76,51 @@ __device__ __forceinline__ f16x4v tr_read(const char* p) {
   return __builtin_bit_cast(f16x4v, v);
 }
 
+// (col, val) of stage s of the ratings p0 .. p0+d-1: lane l holds rating 32 s + (l & 31), clamped to
+// the row (zero weight).  The loads only: wave_ifix finishes the values where they are used, so that
+// nothing waits for them (and for the LDS-DMA issued just before them) at the point of issue.
+template <int KP>
+__device__ __forceinline__ void wave_iload(const SolveArgs& a, int64_t p0, int d, int s, int& c_out, float& r_out) {
+  const int e = WaveRow<KP>::SPS * s + ((threadIdx.x & 63) & 31);
+  const int64_t pe = p0 + (e < d ? e : d - 1);
+  c_out = a.col[pe];
+  r_out = a.val[pe];
+}
+// PRE: past the row end the gather target is the zero row (its products vanish in A' and b').  The
+// rating select is redundant (every use is masked by the same e < d) but stays: without it the copy
+// r_cur = r_nxt waits for the loads behind the DMA again (measured: the whole gain lost)
+template <int KP, bool PRE>
+__device__ __forceinline__ void wave_ifix(const SolveArgs& a, int d, int s, int& c, float& r) {
+  if constexpr (PRE) {
+    const int e = WaveRow<KP>::SPS * s + ((threadIdx.x & 63) & 31);
+    c = e < d ? c : (int)a.zero_row;
+    r = e < d ? r : 0.f;
+  }
+}
+
+// The indices of a row's first two stages.  The kernels issue these loads ahead of the column-scale
+// LDS fill and its workgroup barrier, so that the barrier hides behind them instead of adding a round
+// trip of its own to every row's start-up.
+struct WaveIdx {
+  int c0 = 0, c1 = 0;
+  float r0 = 0.f, r1 = 0.f;
+};
+template <int KP>
+__device__ __forceinline__ WaveIdx wave_prefetch(const SolveArgs& a, int64_t p0, int d) {
+  WaveIdx ix;
+  if (d > 0) wave_iload<KP>(a, p0, d, 0, ix.c0, ix.r0);
+  if (d > WaveRow<KP>::SPS) wave_iload<KP>(a, p0, d, 1, ix.c1, ix.r1);
+  return ix;
+}
+
 // The build of one row's (or split-K chunk's) normal equation by one wave: ratings p0 .. p0+d-1 of
-// the CSR, gathered 32 per stage into this wave's LDS stage st.  On return acc holds the NT upper
-// tiles of Σ c·(cs z)(cs z)ᵀ (still column-scaled), bacc[A] (lane i + 16q) b'[16A + i] unscaled;
-// returns the number of positive ratings.
+// the CSR, gathered 32 per stage into this wave's LDS stage st; ix: wave_prefetch of the row.  On
+// return acc holds the NT upper tiles of Σ c·(cs z)(cs z)ᵀ (still column-scaled), bacc[A] (lane
+// i + 16q) b'[16A + i] unscaled; returns the number of positive ratings.
 template <int KP, bool IMPLICIT, bool PRE>
-__device__ __forceinline__ int wave_build(const SolveArgs& a, int64_t p0, int d, char* st, const float* s_cs,
-                                          f32x4 (&acc)[WaveRow<KP>::NT], float (&bacc)[WaveRow<KP>::NQ]) {
+__device__ __forceinline__ int wave_build(const SolveArgs& a, int64_t p0, int d, const WaveIdx& ix, char* st,
+                                          const float* s_cs, f32x4 (&acc)[WaveRow<KP>::NT],
+                                          float (&bacc)[WaveRow<KP>::NQ]) {
   using W = WaveRow<KP>;
   constexpr int NQ = W::NQ, NT = W::NT;
   const int lane = threadIdx.x & 63, q = lane >> 4, i16 = lane & 15;
@@ -96,17 +134,7 @@ __device__ __forceinline__ int wave_build(const SolveArgs& a, int64_t p0, int d,
   for (int e = 0; e < CPL; ++e) bpart[e] = 0.f;
   int npos = 0;
 
-  // (col, val) of stage s: lane l holds rating 32 s + (l & 31), clamped to the row (zero weight)
-  auto iload = [&](int s, int& c_out, float& r_out) {
-    const int e = W::SPS * s + (lane & 31);
-    const int64_t pe = p0 + (e < d ? e : d - 1);
-    c_out = a.col[pe];
-    r_out = a.val[pe];
-    if constexpr (PRE) {  // past the row end: the zero row (its products vanish in A' and b')
-      c_out = e < d ? c_out : (int)a.zero_row;
-      r_out = e < d ? r_out : 0.f;
-    }
-  };
+  auto iload = [&](int s, int& c_out, float& r_out) { wave_iload<KP>(a, p0, d, s, c_out, r_out); };
   // gather of one stage: piece u holds ratings RPI·u .. RPI·u + RPI-1, lane l the 16 B at
   // 4·(l % LPR) of rating RPI·u + l / LPR; the rating's src row is wave-uniform (readlane)
   auto dma = [&](int cidx) {
@@ -132,19 +160,19 @@ __device__ __forceinline__ int wave_build(const SolveArgs& a, int64_t p0, int d,
     });
   };
 
-  int c_cur = 0, c_nxt = 0;
-  float r_cur = 0.f, r_nxt = 0.f;
+  int c_cur = ix.c0, c_nxt = ix.c1;
+  float r_cur = ix.r0, r_nxt = ix.r1;
   // the stage's fragments are in registers: refill the stage with s + 1, fetch the indices of s + 2
   auto next_stage = [&](int s) {
+    wave_ifix<KP, PRE>(a, d, s + 1, c_nxt, r_nxt);
     dma(c_nxt);
     c_cur = c_nxt;
     r_cur = r_nxt;
     if (s + 2 < nst) iload(s + 2, c_nxt, r_nxt);
   };
   if (nst > 0) {
-    iload(0, c_cur, r_cur);
+    wave_ifix<KP, PRE>(a, d, 0, c_cur, r_cur);
     dma(c_cur);
-    if (nst > 1) iload(1, c_nxt, r_nxt);
   }
   f32x4 bt = zero4();  // PRE: b' of every block in one tile (column 2A: w hi, 2A + 1: w lo)
   for (int s = 0; s < nst; ++s) {
@@ -288,14 +316,33 @@ __global__ __launch_bounds__(256, 2) void solve_wave_kernel(SolveArgs a) {
   const int lane = threadIdx.x & 63, q = lane >> 4, i16 = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar: LDS-DMA bases in SGPRs
   float* s_cs = reinterpret_cast<float*>(lds + W::WAVES * W::LDS_WAVE);  // [KP] scales, [KP] inverses
-  for (int e = threadIdx.x; e < 2 * KP; e += 256) s_cs[e] = a.colscale[e];
-  __syncthreads();  // the only workgroup barrier: every wave below is on its own row
+  // Start-up: the column scales, the row's descriptor and the indices of its first two stages are all
+  // in flight before the LDS fill and the barrier (the only one: every wave below is on its own row).
+  // A wave past the last row reads no descriptor and no index, and still reaches the barrier.
+  static_assert(2 * KP <= 256, "one column-scale load per thread");
+  const float csv = (int)threadIdx.x < 2 * KP ? a.colscale[threadIdx.x] : 0.f;
   const int64_t ridx = (int64_t)blockIdx.x * W::WAVES + wave;
-  if (ridx >= a.n_rows) return;
+  const bool live = ridx < a.n_rows;  // wave-uniform
+  int j = 0, d = 0;
+  int64_t p0 = 0;
+  if (live) {
+    if (a.desc) {  // {row, p0 lo, p0 hi, degree}: one scalar s_load_dwordx4 (constant address space)
+      typedef __attribute__((address_space(4))) const int cint;
+      cint* dq = (cint*)(a.desc) + 4 * ridx;
+      j = dq[0];
+      p0 = (int64_t)(uint32_t)dq[1] | ((int64_t)dq[2] << 32);
+      d = dq[3];
+    } else {
+      j = a.rows[ridx];
+      p0 = a.ptr[j];
+      d = (int)(a.ptr[j + 1] - p0);
+    }
+  }
+  const WaveIdx ix = wave_prefetch<KP>(a, p0, d);
+  if ((int)threadIdx.x < 2 * KP) s_cs[threadIdx.x] = csv;
+  __syncthreads();
+  if (!live) return;
   char* st = lds + wave * W::LDS_WAVE;
-  const int j = a.rows[ridx];
-  const int64_t p0 = a.ptr[j];
-  const int d = (int)(a.ptr[j + 1] - p0);
   f32x4 acc[NT];
   float bacc[NQ];
   WAVE_STAMP(ridx, 0);
@@ -309,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void solve_wave_kernel(SolveArgs a) {
   });
   const int npos = d;
 #else
-  const int npos = wave_build<KP, IMPLICIT, PRE>(a, p0, d, st, s_cs, acc, bacc);
+  const int npos = wave_build<KP, IMPLICIT, PRE>(a, p0, d, ix, st, s_cs, acc, bacc);
 #endif
   WAVE_STAMP(ridx, 1);
   const float lamn = a.reg * (float)(IMPLICIT ? npos : d);
@@ -407,18 +454,28 @@ __global__ __launch_bounds__(256, 2) void wave_partial_kernel(SolveArgs a, Split
   const int lane = threadIdx.x & 63, q = lane >> 4, i16 = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* s_cs = reinterpret_cast<float*>(lds + W::WAVES * W::LDS_WAVE);
-  for (int e = threadIdx.x; e < 2 * KP; e += 256) s_cs[e] = a.colscale[e];
-  __syncthreads();
+  // as solve_wave_kernel: the chunk's addressing and first indices in flight before the barrier
+  static_assert(2 * KP <= 256, "one column-scale load per thread");
+  const float csv = (int)threadIdx.x < 2 * KP ? a.colscale[threadIdx.x] : 0.f;
   const int64_t slot = (int64_t)blockIdx.x * W::WAVES + wave;
-  if (slot >= sp.n_chunks) return;
+  const bool live = slot < sp.n_chunks;  // wave-uniform
+  int j = 0, d = 0;
+  int64_t p0 = 0;
+  if (live) {
+    j = sp.chunk_row[slot];
+    const int64_t rp0 = a.ptr[j], off = (int64_t)sp.chunk_idx[slot] * sp.chunk_len;
+    const int64_t rest = a.ptr[j + 1] - rp0 - off;
+    d = (int)(rest < sp.chunk_len ? rest : sp.chunk_len);
+    p0 = rp0 + off;
+  }
+  const WaveIdx ix = wave_prefetch<KP>(a, p0, d);
+  if ((int)threadIdx.x < 2 * KP) s_cs[threadIdx.x] = csv;
+  __syncthreads();
+  if (!live) return;
   char* st = lds + wave * W::LDS_WAVE;
-  const int j = sp.chunk_row[slot];
-  const int64_t rp0 = a.ptr[j], off = (int64_t)sp.chunk_idx[slot] * sp.chunk_len;
-  const int64_t rest = a.ptr[j + 1] - rp0 - off;
-  const int d = (int)(rest < sp.chunk_len ? rest : sp.chunk_len);
   f32x4 acc[NT];
   float bacc[NQ];
-  const int npos = wave_build<KP, IMPLICIT, PRE>(a, rp0 + off, d, st, s_cs, acc, bacc);
+  const int npos = wave_build<KP, IMPLICIT, PRE>(a, p0, d, ix, st, s_cs, acc, bacc);
   float* out = sp.partial + slot * R::FLOATS;
   const float* isc = s_cs + KP;
   static_for<0, NQ>([&](auto AA) {
@@ -479,6 +536,7 @@ hipError_t launch_solve_wave(int KP, const SolveArgs& a, hipStream_t s) {
     for (int64_t r0 = 0; r0 < a.n_rows; r0 += MAXR) {
       SolveArgs b = a;
       b.rows = a.rows + r0;
+      if (a.desc) b.desc = a.desc + 4 * r0;
       b.n_rows = a.n_rows - r0 < MAXR ? a.n_rows - r0 : MAXR;
       const hipError_t e = launch_solve_wave(KP, b, s);
       if (e != hipSuccess) return e;

@@ -34,7 +34,7 @@ struct SolveArgs {
   // uniform confidence (every rating of the side has the same c: binary implicit data, or explicit):
   // the heavy build gathers pre-split rows instead of Z (launch_presplit), null otherwise
   const void* Zhl;         // [*][2·KP] fp16: hi of √c·colscale·z, then lo
-  int64_t zero_row;        // an all-zero row of Zhl (the gather target of ratings past a row's end)
+  int64_t zero_row;        // an all-zero row of Zhl and of Z (the gather target of ratings past a row's end or masked)
   float wsc;               // power-of-two scale of the rating weights w in the b' MFMA (max|w|·wsc < 2^13)
   float inv_sw;            // 1 / √c
   const int32_t* desc;     // light launches: int4 {row, p0 lo, p0 hi, degree} per entry of `rows` (or null)
