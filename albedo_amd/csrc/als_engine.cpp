@@ -938,6 +938,7 @@ int half_sweep(als_ctx* c, int t) {
   const bool multi = c->world > 1;
   bool have_cmax = false, cs_done = false, split_done = false;
   bool force_heavy = c->p.light_max_degree == 0;
+  bool singular = false;  // regParam = 0 and min Λ <= 1e-12 max Λ
   // world > 1: the previous half's factor gathers (second stream) finish before any collective or
   // rotation of this one is issued -- two RCCL operations of one communicator must never overlap
   if (multi) HIPCHK(hipStreamWaitEvent(st, c->evc[8], 0));
@@ -964,13 +965,17 @@ int half_sweep(als_ctx* c, int t) {
       double wmm[2] = {0.0, 0.0};
       HIPCHK(hipMemcpyAsync(wmm, eig_minmax(c->d_eig.as<double>(), KP), 16, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
-      if (!(wmm[0] > 1e-12 * wmm[1])) force_heavy = true;
+      if (!(wmm[0] > 1e-12 * wmm[1])) force_heavy = singular = true;
     }
     HIPCHK(hipEventRecord(ev[2], st));
     // world > 1: every rank rotates the whole gathered src (no collective on the critical path)
     const float* Xs = multi ? S.d_Xfull.as<float>() : S.d_X.as<float>();
     const int64_t ns = multi ? S.prows() : S.own_n;
-    if (rotate_bf_on(c)) {
+    // regParam = 0 on a near-singular Gram: nothing but Σ c z² stands on the diagonal of a small
+    // eigen-direction, and that bound's floor of 1e-6 λ_max is decades above its column of Z, whose fp16
+    // hi + lo split then keeps too few bits (1.3e-4 on a row at rank 128 with one src column at 2^-22).
+    // Such a half takes the fp32 rotation below, whose column scales come from the measured maxima.
+    if (rotate_bf_on(c) && !singular) {
       // bf16 MFMA rotation with the heavy build's split in the same pass.  Its column scales come
       // first, from a bound: Σ_i Z_ij² = p_jᵀ G p_j, which is λ_j up to the fp32 rounding of P and of
       // the product (≤ 1e-6 λ_max), so max_i |Z_ij| ≤ √(λ_j + 1e-6 λ_max).  The split's fp16 range
@@ -1072,7 +1077,7 @@ int half_sweep(als_ctx* c, int t) {
   HIPCHK(hipStreamSynchronize(st));
   // Cholesky path: the device eigensolver's Jacobi sweeps (als_solver_stats), decoded like
   // als_device_eigh (eig.hip stores -(sweeps + 1) when the budget ran out)
-  T.solver[0] = sweeps < 0 ? -sweeps - 1 : sweeps;
+  T.solver[0] = sweeps == EIG_NOT_FINITE ? 0 : (sweeps < 0 ? -sweeps - 1 : sweeps);
   T.solver[1] = T.solver[2] = T.solver[3] = 0;
   T.t[ALS_T_GRAM] = event_ms(ev[0], ev[1]);
   T.t[ALS_T_EIG] = event_ms(ev[1], ev[2]);  // device eigensolver + the new basis
@@ -1086,6 +1091,11 @@ int half_sweep(als_ctx* c, int t) {
     T.t[ALS_T_SOLVE_HEAVY] = event_ms(ev[5], ev[6]);
   }
   T.t[ALS_T_HALF_TOTAL] = event_ms(ev[0], ev[6]);
+  if (sweeps == EIG_NOT_FINITE)  // eig.hip: a NaN or an Inf in the Gram (non-finite src factors, or norms past fp32)
+    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
+                std::string("the ") + (t == ALS_USER ? "item" : "user") +
+                    " Gram matrix is not finite (NaN or Inf in the source factors, or row norms past fp32): "
+                    "the eigensolver did not converge");
   if (sweeps < 0)  // eig.hip: the Jacobi sweep budget ran out (the host eigensolver's "did not converge")
     return fail(ALS_E_NOT_POSITIVE_DEFINITE, "eigensolver did not converge (device Jacobi: " +
                                                  std::to_string(-sweeps - 1) + " sweeps without meeting the tolerance)");
@@ -2610,7 +2620,9 @@ int als_device_eigh(int32_t device, int32_t k, const double* g, const double* w0
     w[i] = wk[i];
     for (int j = 0; j < k; ++j) v[(size_t)i * k + j] = P[(size_t)i * KP + j];
   }
-  if (sweeps) *sweeps = sw < 0 ? -sw - 1 : sw;
+  if (sweeps) *sweeps = sw == EIG_NOT_FINITE ? 0 : (sw < 0 ? -sw - 1 : sw);
+  if (sw == EIG_NOT_FINITE)
+    return fail(ALS_E_NOT_POSITIVE_DEFINITE, "the matrix is not finite (NaN or Inf): eigensolver did not converge");
   if (sw < 0) return fail(ALS_E_NOT_POSITIVE_DEFINITE, "eigensolver did not converge");
   return ALS_OK;
 }

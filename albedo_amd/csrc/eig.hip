@@ -42,6 +42,8 @@ constexpr int JAC_THREADS = 1024;
 // count (-(sweeps + 1)), and the engine fails the half-sweep as the host eigensolver it replaced did
 // (ALS_E_NOT_POSITIVE_DEFINITE, "did not converge"): the light push-through solves assume Λ is the
 // diagonal of the Gram in the basis P.  ALBEDO_JAC_MAX_SWEEPS lowers the budget (test knob).
+// A matrix with a NaN or an Inf (its off-diagonal or diagonal mass is then not finite) ends at once
+// with EIG_NOT_FINITE: `!(off > tol·dia)` alone would call it converged in 0 sweeps.
 constexpr int JAC_MAX_SWEEPS = 30;
 int jacobi_max_sweeps() {
   const char* e = std::getenv("ALBEDO_JAC_MAX_SWEEPS");
@@ -52,8 +54,27 @@ int jacobi_max_sweeps() {
 // about fp64 rounding at k <= 256: a backward error of the order of a Householder + QL solve).  The
 // small eigenpairs need it: at 1e-9 the directions of eigenvalues near 1e-9·‖G‖ keep components of the
 // large ones, and the per-row systems built on them (D = Λ + λn, push-through S = Z D⁻¹ Zᵀ) lose
-// positive definiteness in fp32.  Below 1e-20, a sweep that does not halve the mass (the rounding floor) also stops.
+// positive definiteness in fp32.
+// JAC_SKIP: a pair whose |a_pq| is at most 2^-53 of the diagonal's root mean square, and whose
+// |a_qq - a_pp| is within 2^10 of that (JAC_NEAR), is not rotated.  Such an a_pq is rounding noise of
+// the sweeps themselves, and rotating it is not harmless: inside a group of equal eigenvalues (the
+// k - n zeros of a Gram of n < k rows, the copies of G = cI) a_qq - a_pp is noise as well, the angle is
+// anything up to 45 degrees, and the rotation mixes the couplings of p and q to the other
+// eigenvalues, those already annihilated in this sweep with those still to come.  Every pair used to
+// rotate unless a_pq was exactly 0, and such matrices left the quadratic regime near a mass of 1e-19
+// and went on at 0.4 - 0.55 per sweep: 30 sweeps where 10 do (tests/test_gpu_gram_eig_edges.py,
+// `deficient` at k = 64; a half-sweep between two rank-deficient sides spent the whole budget).
+// A noise-level a_pq between well separated diagonal entries still rotates, by a negligible angle, so
+// a matrix without coinciding eigenvalues is swept as it always was.
+// Below JAC_STALL a sweep that does not halve the mass also stops (the rounding floor).  That bound
+// was 1e-20 once, and the first sweep at 0.55 in the slow regime above ended the run with an
+// off-diagonal norm of 1e-10 ‖G‖; 1e-25 leaves at most 3e-13 ‖G‖.  A run that spends the budget is
+// still accepted at JAC_ACCEPT = 1e-20, where it used to stop at its first slow sweep.
 constexpr double JAC_TOL = 1e-28;
+constexpr double JAC_SKIP = 0x1p-53;
+constexpr double JAC_NEAR = 0x1p20;  // (2^10)^2: compared with squares
+constexpr double JAC_STALL = 1e-25;
+constexpr double JAC_ACCEPT = 1e-20;
 
 // round r of the round-robin over n (even) players: pair i = (a, b); player n-1 is fixed
 __device__ __forceinline__ void rr_pair(int r, int i, int n, int& a, int& b) {
@@ -81,6 +102,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_kernel(double* __restrict_
   __shared__ int pq[2 * 128];     // p, q
   __shared__ double red[JAC_THREADS / 64][2];
   __shared__ int done;
+  __shared__ double skip2;     // the sweep's rotation threshold, squared (JAC_SKIP)
   double prev_off = INFINITY;  // thread 0's
   const int ld = LDSM ? k + 1 : KP;  // LDS: padded row stride (column walks spread over the banks)
   double* M = LDSM ? sm : Mg;
@@ -115,9 +137,11 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_kernel(double* __restrict_
         so += red[i][0];
         sd += red[i][1];
       }
-      done = !(so > JAC_TOL * sd) || (!(so > 1e-20 * sd) && !(so < 0.5 * prev_off));  // or at the rounding floor
-      if (!done && sweep >= max_sweeps) done = 2;  // the sweep budget is spent: not converged
+      done = !(so > JAC_TOL * sd) || (!(so > JAC_STALL * sd) && !(so < 0.5 * prev_off));  // or stalled, see JAC_STALL
+      if (!done && sweep >= max_sweeps) done = so > JAC_ACCEPT * sd ? 2 : 1;  // the sweep budget is spent
+      if (!(so + sd < INFINITY)) done = 3;  // a NaN / Inf mass fails every comparison above: no sweep can help
       prev_off = so;
+      skip2 = JAC_SKIP * JAC_SKIP * (sd / k);
     }
     __syncthreads();
     if (done) break;
@@ -128,8 +152,9 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_kernel(double* __restrict_
         double c = 1.0, s = 0.0;
         if (q < k) {
           const double apq = M[p * ld + q];
-          if (apq != 0.0) {
-            const double th = (M[q * ld + q] - M[p * ld + p]) / (2.0 * apq);
+          const double dqp = M[q * ld + q] - M[p * ld + p];
+          if (apq != 0.0 && !(apq * apq <= skip2 && dqp * dqp <= JAC_NEAR * skip2)) {
+            const double th = dqp / (2.0 * apq);
             const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(fma(th, th, 1.0)));
             c = 1.0 / sqrt(fma(t, t, 1.0));
             s = t * c;
@@ -175,7 +200,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_kernel(double* __restrict_
     }
   }
   for (int i = tid; i < KP; i += JAC_THREADS) w[i] = i < k ? M[i * ld + i] : 0.0;
-  if (tid == 0 && sweeps_out) *sweeps_out = done == 2 ? -sweep - 1 : sweep;  // < 0: did not converge
+  if (tid == 0 && sweeps_out) *sweeps_out = done == 3 ? EIG_NOT_FINITE : (done == 2 ? -sweep - 1 : sweep);  // < 0: did not converge
 }
 
 // k <= 128: JAC_WG workgroups sweep identical copies of M in LDS (same code, same inputs, fixed
@@ -192,6 +217,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_lds_kernel(const double* _
   __shared__ int pq[2 * 64];
   __shared__ double red[JAC_THREADS / 64][2];
   __shared__ int done;
+  __shared__ double skip2;     // the sweep's rotation threshold, squared (JAC_SKIP)
   double prev_off = INFINITY;  // thread 0's
   const int ld = k + 1;           // M row stride (column walks spread over the banks)
   const int nc = KP / JAC_WG;     // VT columns of this workgroup
@@ -228,9 +254,11 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_lds_kernel(const double* _
         so += red[i][0];
         sd += red[i][1];
       }
-      done = !(so > JAC_TOL * sd) || (!(so > 1e-20 * sd) && !(so < 0.5 * prev_off));  // or at the rounding floor
-      if (!done && sweep >= max_sweeps) done = 2;  // the sweep budget is spent: not converged
+      done = !(so > JAC_TOL * sd) || (!(so > JAC_STALL * sd) && !(so < 0.5 * prev_off));  // or stalled, see JAC_STALL
+      if (!done && sweep >= max_sweeps) done = so > JAC_ACCEPT * sd ? 2 : 1;  // the sweep budget is spent
+      if (!(so + sd < INFINITY)) done = 3;  // a NaN / Inf mass fails every comparison above: no sweep can help
       prev_off = so;
+      skip2 = JAC_SKIP * JAC_SKIP * (sd / k);
     }
     __syncthreads();
     if (done) break;
@@ -241,8 +269,9 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_lds_kernel(const double* _
         double c = 1.0, s = 0.0;
         if (q < k) {
           const double apq = M[p * ld + q];
-          if (apq != 0.0) {
-            const double th = (M[q * ld + q] - M[p * ld + p]) / (2.0 * apq);
+          const double dqp = M[q * ld + q] - M[p * ld + p];
+          if (apq != 0.0 && !(apq * apq <= skip2 && dqp * dqp <= JAC_NEAR * skip2)) {
+            const double th = dqp / (2.0 * apq);
             const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(fma(th, th, 1.0)));
             c = 1.0 / sqrt(fma(t, t, 1.0));
             s = t * c;
@@ -289,7 +318,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_lds_kernel(const double* _
   for (int e = tid; e < KP * nc; e += JAC_THREADS) VTg[(e / nc) * KP + c0 + e % nc] = VT[e];
   if (blockIdx.x == 0) {
     for (int i = tid; i < KP; i += JAC_THREADS) w[i] = i < k ? M[i * ld + i] : 0.0;
-    if (tid == 0 && sweeps_out) *sweeps_out = done == 2 ? -sweep - 1 : sweep;  // < 0: did not converge
+    if (tid == 0 && sweeps_out) *sweeps_out = done == 3 ? EIG_NOT_FINITE : (done == 2 ? -sweep - 1 : sweep);  // < 0: did not converge
   }
 }
 

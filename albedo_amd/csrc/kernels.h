@@ -124,6 +124,7 @@ hipError_t launch_device_eig(int KP, int k, const double* G, const double* Bs, c
                              double* scratch, float* P32, float* lam32, unsigned* ub, hipStream_t s);
 const double* eig_minmax(const double* scratch, int KP);  // device {min Λ, max Λ} of the last call
 const int* eig_sweeps(const double* scratch, int KP);     // device Jacobi sweep count of the last call
+constexpr int EIG_NOT_FINITE = -(1 << 30);                 // ... its value when the matrix held a NaN or an Inf
 hipError_t launch_identity(double* B, int KP, hipStream_t s);
 hipError_t launch_basis_t32(const double* B, float* Bt, int KP, hipStream_t s);  // Bt = (float) Bᵀ
 
