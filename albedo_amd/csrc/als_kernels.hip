@@ -1836,6 +1836,7 @@ __device__ void nnls_reg_iterate(const SolveArgs& a, float* smem, int j, int ite
         for (int w = 1; w < R::NJS; ++w) y += sP[w * KP + c_own];
         axi = (double)y;
       }
+      last_wall = iterno - 1;  // restart CG: the last direction is not conjugate to the refreshed residual
     }
     // residual = A x - b ; projected gradient
     const double res = own ? axi - (double)bi : 0.0;
@@ -2030,6 +2031,10 @@ __global__ __launch_bounds__(Heavy<KP>::NTH) void solve_nnls_kernel(SolveArgs a,
       nt_symv<KP, 1>(smem, vv, yy, wsc, ot);
       __syncthreads();
       if (own) axi = (double)y0[i];
+      // the refreshed residual differs from the carried one by the fp32 rounding of x and of the product,
+      // so the last direction is no longer conjugate to it: restart CG from the gradient, as after a
+      // wall hit (a row about to stop at a refresh otherwise ran on for several more refreshes)
+      last_wall = iterno - 1;
     }
     // residual = A x - b ; projected gradient
     const double res = own ? axi - bi : 0.0;

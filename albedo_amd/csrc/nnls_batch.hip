@@ -432,6 +432,11 @@ __global__ __launch_bounds__((NBatch<KP, SV>::NTH), 1) void nnls_batch_kernel(So
       for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
         for (int t = 0; t < 4; ++t) ax[rb][t] = (double)yo[0][rb][t];
+      // the refreshed residual differs from the carried one by the fp32 rounding of x and of the
+      // product, so the last direction (and its A·lastDir, lastDir·A·lastDir) is no longer conjugate to
+      // it: restart CG from the gradient, as after a wall hit.  Without it a row about to stop at a
+      // refresh ran on for several more refreshes (259 iterations against Spark's 72).
+      last_wall = iterno - 1;
     }
     ++wg_iter;
     BT_PH(1);

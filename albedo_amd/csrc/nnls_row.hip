@@ -415,6 +415,7 @@ __device__ __forceinline__ void nnls_row_body(const SolveArgs& a, const float* _
       (void)product();
       __syncthreads();
       if (own) axi = (double)ysum();
+      last_wall = iterno - 1;  // restart CG: the last direction is not conjugate to the refreshed residual
       NR_PH(6);
     }
     // residual = A x - b ; projected gradient

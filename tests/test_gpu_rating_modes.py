@@ -28,6 +28,7 @@ import pytest
 from oracle import cbind
 from oracle import spark_als as O
 from tests import ladder as LD
+from tests import nnls_cases as NC
 from tests.test_gpu_parity import Ctx, _rel, _row_rel
 
 pytestmark = pytest.mark.gpu
@@ -159,13 +160,15 @@ def _nnls_path_of(d, KP, chunk):
     return "nnls-lockstep" if d <= lim else ("nnls-split" if 0 < chunk < d else "nnls-row")
 
 
-@pytest.mark.parametrize("k,chunk", [(50, None), (256, None), (256, "256")],
-                         ids=["k50-chunkdefault", "k256-chunkdefault", "k256-chunk256"])
+@pytest.mark.parametrize("k,chunk", [(50, None), (100, None), (128, None), (256, None), (256, "256")],
+                         ids=["k50-chunkdefault", "k100-chunkdefault", "k128-chunkdefault", "k256-chunkdefault", "k256-chunk256"])
 @pytest.mark.parametrize("mode", ["mixed", "stars", "stars_signed"])
 def test_nnls_rating_modes(gpu_lib, monkeypatch, tmp_path, mode, k, chunk):
     """nonnegative = true on the ladder: the item half runs the per-row kernels (and split-K + the
     prebuilt NNLS at a chunk of 256), the user half the lockstep kernel, against the C restatement of
-    Spark's NNLSSolver (pinned to the numpy oracle in these modes by tests/test_oracle.py)."""
+    Spark's NNLSSolver (pinned to the numpy oracle in these modes by tests/test_oracle.py): the
+    whole-matrix checks, and every row through the per-row check of tests/nnls_cases.py (sign, exact zero
+    rows, KKT residual, the row's own distance, the row's zero pattern)."""
     implicit, alpha, reg = LD.MODES[mode]
     ch = _set_chunk(monkeypatch, chunk)
     KP = LD.padded_rank(k)
@@ -190,6 +193,7 @@ def test_nnls_rating_modes(gpu_lib, monkeypatch, tmp_path, mode, k, chunk):
         else:
             assert np.sum(paths == "nnls-row") >= 2 and (chunk is None or np.sum(paths == "nnls-split") >= 2)
         X_ref, _ = cbind.solve_rows_nnls(src, O.gram(src), ptr, col, val, reg=reg, alpha=alpha, implicit=implicit)
+        ref = NC.reference(src, ptr, col, val, reg=reg, alpha=alpha, implicit=implicit)
         name = "item" if side else "user"
         same = float(np.mean((X == 0) == (X_ref == 0)))
         print(f"RATING_MODES {tag} KP {KP} {name} half: rel {_rel(X, X_ref):.3e}, equal zero pattern {same:.5f}")
@@ -197,6 +201,9 @@ def test_nnls_rating_modes(gpu_lib, monkeypatch, tmp_path, mode, k, chunk):
         # max over the rows of max|x - ref| / max|ref of all rows| is _rel(X, X_ref)
         LD.assert_rows(X, X_ref, ids, deg, paths, 1e-3, f"{name} half [{tag}]", tmp_path, global_scale=True)
         assert same > 0.995
+        rows = np.array([NC.nnls_path_of(d, KP, ch) for d in deg])
+        assert NC.is_lockstep(rows).tolist() == lock.tolist()
+        NC.check_rows(X, ref, ids, deg, rows, f"{name} half per row [{tag}]", tmp_path, NC.KKT_MARGIN)
         src = X
 
 

@@ -933,3 +933,218 @@ def test_row_count_cases_expose_a_gram_that_drops_the_last_row(k):
         G = O.gram(F)
         miss = np.abs(O.gram(F[:-1]) - G).max() / np.abs(G).max()
         assert miss > 1e-6, (n, miss)
+
+
+# ---- the NNLS edge cases (tests/nnls_cases.py) ----------------------------------------------------
+
+def test_nnls_path_restatement_against_the_table_of_limits():
+    """nnls_cases.nnls_path_of against the lockstep limits YBUDGET / (slots * KP) capped by the light limit
+    (KP 64: 24 | 32; KP 128: 12 | 24, then 48 | 64 behind ALBEDO_NNLS_MIN_SLOTS; KP 256: 6 | 12, then
+    24 | 48 | 64), the per-row labels and their split forms."""
+    from tests import nnls_cases as NC
+    table = {(64, 8): [(16, 24), (8, 32)], (64, 1): [(16, 24), (8, 32)],
+             (128, 8): [(16, 12), (8, 24)], (128, 4): [(16, 12), (8, 24), (4, 48)],
+             (128, 1): [(16, 12), (8, 24), (4, 48), (2, 64)],
+             (256, 16): [(16, 6)], (256, 8): [(16, 6), (8, 12)], (256, 4): [(16, 6), (8, 12), (4, 24)],
+             (256, 2): [(16, 6), (8, 12), (4, 24), (2, 48)], (256, 1): [(16, 6), (8, 12), (4, 24), (2, 48), (1, 64)]}
+    for (KP, ms), rows in table.items():
+        assert [(sv, hi) for sv, (_, hi) in NC.variant_ranges(KP, ms).items()] == rows, (KP, ms)
+        lo = 1
+        for sv, hi in rows:
+            for d in (lo, hi):
+                assert NC.nnls_path_of(d, KP, 8192, ms) == f"lockstep-{sv}", (KP, ms, d)
+            lo = hi + 1
+        assert NC.nnls_path_of(lo, KP, 8192, ms) == f"row-{KP}"
+        assert NC.nnls_path_of(256, KP, 256, ms) == f"row-{KP}" and NC.nnls_path_of(257, KP, 256, ms) == f"row-{KP}-split"
+        assert NC.nnls_path_of(9000, KP, 0, ms) == f"row-{KP}"
+    assert NC.batch_limits(256, 3) == NC.batch_limits(256, 8)  # an invalid knob value is the default
+    assert NC.nnls_path_of(65, 256, 256, 8, "1024") == "row-256-1024" and NC.nnls_path_of(513, 256, 256, 8, "1024") == "row-256-1024-split"
+    assert NC.nnls_path_of(65, 128, 256, 8, "1024") == "row-128"
+    assert NC.path_stats([3, 30, 300], ["lockstep-16", "row-64", "row-64-split"]) == [1, 3, 2, 330]
+
+
+def test_nnls_ladder_reaches_every_expected_path():
+    """The NNLS ladder holds every degree twice; under every configuration of tests/test_gpu_nnls_edges.py
+    each expected label holds at least 2 rows, and every lockstep variant that can hold a row has at least
+    2 rows at its limit and 2 one above it, on another path."""
+    from tests import ladder as LD
+    from tests import nnls_cases as NC
+    user, item, r, B = NC.ladder_data("varying")
+    assert np.unique(user.astype(np.int64) << 32 | item).size == user.size and np.any(np.diff(user) < 0)
+    deg_i, deg_u = np.diff(B.i_ptr), np.diff(B.u_ptr)
+    assert sorted(deg_i.tolist()) == sorted(NC.NNLS_LADDER + NC.NNLS_LADDER)
+    assert 650 <= len(B.user_ids) <= 700 and 6 < deg_u.max() <= 12
+    for k in (50, 100, 128, 256):
+        KP = LD.padded_rank(k)
+        for chunk in (8192, 256):
+            for ms in (8, 4, 1):
+                for rk in (None, "1024"):
+                    paths = np.array([NC.nnls_path_of(d, KP, chunk, ms, rk) for d in deg_i])
+                    want = NC.expected_nnls_paths(KP, chunk, ms, int(deg_i.max()), rk)
+                    assert set(paths.tolist()) == set(want), (k, chunk, ms, rk)
+                    assert all(np.sum(paths == p) >= 2 for p in want), (k, chunk, ms)
+                    for sv, (at, above) in NC.boundary_rows(deg_i, paths, KP, ms).items():
+                        assert at >= 2 and above >= 2, (k, ms, sv)
+        upaths = np.array([NC.nnls_path_of(d, KP, 8192) for d in deg_u])
+        assert set(upaths.tolist()) == set(NC.expected_nnls_paths(KP, 8192, 8, int(deg_u.max())))
+        assert all(np.sum(upaths == p) >= 2 for p in set(upaths.tolist()))
+    assert set(NC.variant_ranges(256, 1)) == {16, 8, 4, 2, 1} and set(NC.variant_ranges(128, 1)) == {16, 8, 4, 2}
+    for mode in LD.MODES:
+        Bm = NC.ladder_data(mode)[3]
+        if mode == "mixed":
+            assert np.sum(np.add.reduceat(Bm.i_val > 0, Bm.i_ptr[:-1]) == 0) >= 4
+    # the row-count cases: every row on the one variant they name
+    from tests.test_gpu_nnls_edges import ROW_COUNT_CASES
+    assert {sv for _, sv, *_ in ROW_COUNT_CASES} == {16, 8, 1}
+    for k, sv, ms, d, n, _ in ROW_COUNT_CASES:
+        u, i = NC.uniform_degree_coo(n, d)
+        Bn = O.make_blocks(u, i, np.ones(u.size, np.float32))
+        assert np.diff(Bn.i_ptr).tolist() == [d] * n and n >= 1
+        assert NC.nnls_path_of(d, LD.padded_rank(k), 8192, ms or 8) == f"lockstep-{sv}"
+
+
+@pytest.mark.parametrize("k", [50, 128, 256])
+def test_nnls_scale_cases_are_decided_by_the_absolute_step_threshold(k):
+    """Src rows of norm 2^10: the first step (g·res) / (g·A·g) at x = 0 of every row is below 1e-7 / 8, so
+    Spark stops at once and returns exactly 0 after 0 iterations; at 2^-10 every row iterates and none is
+    zero.  The same rows at unit norm iterate too."""
+    from tests import nnls_cases as NC
+    big = NC.item_reference("varying", k, "large")
+    steps = []
+    for j in range(len(big.it)):
+        A, b, n = O.normal_equation(big.src, big.ptr, big.col, big.val, j, True, big.alpha, big.G)
+        A = A + big.reg * n * np.eye(k)
+        res = -b
+        g = np.where(res > 0, 0.0, res)
+        steps.append(float(g @ res) / (float(g @ A @ g) + 1e-20))
+    assert 0 < min(steps) and max(steps) < 1e-7 / 8, (min(steps), max(steps))
+    assert not big.X.any() and not big.it.any()
+    small = NC.item_reference("varying", k, "small")
+    assert small.it.min() >= 1 and small.X.any(axis=1).all()
+    assert np.allclose(np.linalg.norm(small.src, axis=1), 2.0 ** -10, rtol=1e-6)
+    assert np.allclose(np.linalg.norm(big.src, axis=1), 2.0 ** 10, rtol=1e-6)
+
+
+def test_nnls_oracle_iteration_windows():
+    """On every input of the NNLS edge suite the oracle stops by Spark's rule well before the cap
+    max(400, 20 k) (below half of it), so both sides stop at a defined point; regParam = 0 at rank 128 / 256
+    and regParam 1e-3 with alpha 200 at rank 128 have at least 20 rows past 128 iterations (two residual
+    refreshes of the per-row kernels); all-negative src factors give 0 iterations, all-positive ones no
+    zero row and at least 4 rows without a zero."""
+    from tests import nnls_cases as NC
+    many = {("reg0", 128), ("reg0", 256), ("stiff", 128)}
+    for name, (_, _, _, ranks) in NC.PARAM_CASES.items():
+        for k in ranks:
+            ref = NC.item_reference("varying", k, "nonneg", name)
+            assert ref.it.max() < NC.iteration_cap(k) // 2, (name, k, int(ref.it.max()))
+            if (name, k) in many:
+                assert np.sum(ref.it > 128) >= 20, (name, k)
+    for kind in ("nonneg", "aniso", "pos"):
+        for k in (50, 128, 256):
+            ref = NC.item_reference("varying", k, kind)
+            assert 1 <= ref.it.min() and ref.it.max() < NC.iteration_cap(k) // 2, (kind, k)
+            if kind == "pos":
+                assert ref.X.any(axis=1).all() and np.sum((ref.X > 0).all(axis=1)) >= 4  # interior rows
+            if kind == "aniso":
+                d = np.diag(ref.G)
+                assert d.max() / d.min() > 3e3  # G spans about four decades
+    for k in (50, 256):
+        ref = NC.item_reference("varying", k, "neg")
+        assert not ref.X.any() and not ref.it.any() and (ref.src < 0).all()
+    for k in (1, 2):
+        assert (NC.src_factors("nonneg", 20, k) > 0).all()
+    assert (NC.src_factors("nonneg", 20, 3)[:, 2] < 0).all()
+
+
+def test_nnls_check_rows_rejects_what_the_whole_matrix_checks_accept(tmp_path):
+    """The per-row check of the NNLS edge suite on CPU-side mutations of a correct result: a low-norm row
+    scaled by 1.01, an exactly-zero row set to 1e-6, k // 64 + 2 zeros of a row flipped.  The whole-matrix
+    checks (relative error against the largest entry of the matrix < 1e-3, equal zero pattern on > 99.5 %
+    of the entries) accept all three; check_rows names each with its criterion."""
+    from tests import ladder as LD
+    from tests import nnls_cases as NC
+    k = 50
+    user, item, r, B = NC.ladder_data("mixed")
+    r = np.where(item == B.item_ids[np.diff(B.i_ptr) == 5][0], np.float32(2.0 ** -8), r)  # one low-confidence row
+    B = O.make_blocks(user, item, r)
+    ref = NC.reference(NC.src_factors("nonneg", len(B.user_ids), k), B.i_ptr, B.i_col, B.i_val, reg=0.5, alpha=10.0, implicit=True)
+    deg = np.diff(B.i_ptr)
+    paths = np.array([NC.nnls_path_of(d, 64, 8192) for d in deg])
+    margin = 16.0
+
+    def whole_matrix_accepts(X):  # as part of a half of 5 x 52 rows, the others correct
+        err = np.max(np.abs(X.astype(np.float64) - ref.X)) / np.max(np.abs(ref.X))
+        same = (np.sum((X == 0) == (ref.X == 0)) + 4 * X.size) / (5 * X.size)
+        return err < 1e-3 and same > 0.995 and np.all(X >= 0)
+
+    stats = NC.check_rows(ref.X, ref, B.item_ids, deg, paths, "clean", tmp_path, margin)
+    assert set(stats) == set(paths.tolist()) and all(s["err"] == 0 and s["flips"] == 0 for s in stats.values())
+    norms = np.abs(ref.X).max(axis=1)
+    zero = np.nonzero(norms == 0)[0]
+    assert zero.size >= 4
+    low = int(np.argmin(np.where(norms > 0, norms, np.inf)))
+    assert deg[low] == 5 and norms[low] < 0.08 * norms.max()
+    # a low-norm row off by 1 % in every digit
+    X = ref.X.copy()
+    X[low] *= np.float32(1.01)
+    assert whole_matrix_accepts(X)
+    with pytest.raises(AssertionError) as e:
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "scaled row", tmp_path, margin)
+    msg = str(e.value)
+    assert "1 of 52 rows" in msg and f"id {B.item_ids[low]} degree {deg[low]} path {paths[low]} fails" in msg and "d:distance" in msg
+    saved = np.load(msg.rsplit("saved to ", 1)[1].strip())
+    assert saved["ids"].tolist() == [B.item_ids[low]] and np.array_equal(saved["got"][0], X[low])
+    # an exactly-zero row at 1e-6
+    X = ref.X.copy()
+    X[zero[0]] = 1e-6
+    assert whole_matrix_accepts(X)
+    with pytest.raises(AssertionError, match=f"id {B.item_ids[zero[0]]} degree {deg[zero[0]]} ") as e:
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "zero row", tmp_path, margin)
+    assert "b:zero row" in str(e.value)
+    # k // 64 + 2 zeros of one row flipped (to a value the distance criterion cannot see)
+    row = int(np.argmax((ref.X == 0).sum(axis=1) * (norms > 0)))
+    at = np.nonzero(ref.X[row] == 0)[0][:k // 64 + 2]
+    assert at.size == k // 64 + 2
+    X = ref.X.copy()
+    X[row, at] = np.float32(1e-7 * norms[row])
+    assert whole_matrix_accepts(X) and LD.row_errors(X, ref.X).max() < 1e-6
+    with pytest.raises(AssertionError, match=f"id {B.item_ids[row]} degree {deg[row]} ") as e:
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "flipped zeros", tmp_path, margin)
+    assert "e:zero pattern" in str(e.value)
+    # negative and non-finite entries, and a KKT residual the distance does not show
+    X = ref.X.copy()
+    X[low, 0] = -1e-9
+    with pytest.raises(AssertionError, match="a:sign/finite"):
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "negative", tmp_path, margin)
+    X[low, 0] = np.nan
+    with pytest.raises(AssertionError, match="a:sign/finite"):
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "nan", tmp_path, margin)
+    X = ref.X.copy()
+    X[low] *= np.float32(1.0005)  # inside the 1e-3 distance, 5e-4 |b| off the optimum
+    with pytest.raises(AssertionError) as e:
+        NC.check_rows(X, ref, B.item_ids, deg, paths, "kkt", tmp_path, margin)
+    assert "c:kkt" in str(e.value) and "d:distance" not in str(e.value)
+    # the iteration parity: a path that takes 20 % more iterations than the oracle
+    lock, rest = NC.iteration_sums(ref.it, paths)
+    assert lock > 100 and rest > 100
+    assert NC.check_iterations([lock + rest, int(ref.it.max()), 52, lock], ref, paths, k, "clean") == [1.0, 1.0]
+    with pytest.raises(AssertionError, match="lockstep iterations"):
+        NC.check_iterations([int(1.2 * lock) + rest, int(ref.it.max()), 52, int(1.2 * lock)], ref, paths, k, "slow")
+    with pytest.raises(AssertionError, match="iteration cap"):
+        NC.check_iterations([lock + rest, NC.iteration_cap(k), 52, lock], ref, paths, k, "cap")
+    with pytest.raises(AssertionError):
+        NC.check_iterations([lock + rest, int(ref.it.max()), 51, lock], ref, paths, k, "rows")
+
+
+def test_nnls_fit_reference_is_the_numpy_fit():
+    """nnls_cases.fit_reference (the C restatement of NNLS.solve, half-sweep by half-sweep) is O.fit with
+    nonnegative = true; pinned at rank 16, where the numpy loop takes a second (at rank 128 it takes 30 s,
+    which is why the GPU fit test uses the C restatement)."""
+    from tests import nnls_cases as NC
+    user, item, r, B = NC.ladder_data("varying")
+    U0 = NC.src_factors("nonneg", len(B.user_ids), 16)
+    V0 = NC.src_factors("nonneg", len(B.item_ids), 16, seed=77)
+    U, V = O.fit(B, rank=16, max_iter=2, reg=0.5, alpha=10.0, implicit=True, nonnegative=True, init_user=U0, init_item=V0)
+    Uc, Vc = NC.fit_reference(B, U0, max_iter=2, reg=0.5, alpha=10.0, implicit=True)
+    assert np.max(np.abs(U - Uc)) <= 1e-6 * np.max(np.abs(U)) and np.max(np.abs(V - Vc)) <= 1e-6 * np.max(np.abs(V))
+    assert np.array_equal(U == 0, Uc == 0) and np.array_equal(V == 0, Vc == 0)
