@@ -1,4 +1,5 @@
-// libalbedo_als.so host engine: the C ABI of include/albedo_als.h.
+// libalbedo_als.so host engine: the C ABI of include/albedo_als.h, except top-k and NDCG
+// (topk_host.cpp; engine.h is what the two files share).
 //
 // Mirrors Spark MLlib 2.2.0 ALS.train as reached from ALSRecommenderBuilder.scala:46-58:
 //   userFactors = initialize(...); itemFactors = initialize(...)
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "albedo_als.h"
+#include "engine.h"
 #include "host_math.h"
 #include "kernels.h"
 
@@ -36,173 +38,20 @@ namespace {
 thread_local std::string g_err;
 std::mutex g_fork_mu;  // parent / fork lifetimes (als_fork: forks may be destroyed from any thread)
 
-int fail(int code, const std::string& msg) {
+}  // namespace
+
+int albedo::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIPCHK(x)                                                                                  \
-  do {                                                                                             \
-    hipError_t e_ = (x);                                                                           \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(e_ == hipErrorOutOfMemory ? ALS_E_OUT_OF_MEMORY : ALS_E_HIP,                     \
-                  std::string("HIP error: ") + hipGetErrorString(e_) + " in " #x);                 \
-  } while (0)
 #define NCCLCHK(x)                                                                                 \
   do {                                                                                             \
     ncclResult_t r_ = (x);                                                                         \
     if (r_ != ncclSuccess) return fail(ALS_E_RCCL, std::string("RCCL error: ") + ncclGetErrorString(r_) + " in " #x); \
   } while (0)
-#define TRYC(x)                    \
-  do {                             \
-    int rc_ = (x);                 \
-    if (rc_ != ALS_OK) return rc_; \
-  } while (0)
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  bool owned = true;  // false: a view of another context's buffer (als_fork), never freed here
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p && owned) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    owned = true;
-  }
-  void share(const DevBuf& o) {
-    release();
-    p = o.p;
-    bytes = o.bytes;
-    owned = false;
-  }
-  hipError_t ensure(size_t b) {
-    if (!owned) return hipErrorNotSupported;  // a view (als_fork) is never resized or written through
-    if (b <= bytes && p) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&p, b ? b : 16);
-    if (e == hipSuccess) bytes = b;
-    return e;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-enum { B_L16 = 0, B_L32 = 1, B_L64 = 2, B_L96 = 3, B_HEAVY = 4, NBUCKET = 5 };
-
-struct Side {
-  int64_t n = 0;                 // rows (unique raw ids)
-  std::vector<int32_t> ids;      // ascending
-  std::vector<int64_t> starts;   // shard starts over dense rows (world + 1)
-  int64_t maxrows = 0;           // max own rows over ranks
-  // Gathered (padded) layout, chunk-major so that one chunk of every rank is contiguous: rank r's
-  // local row i sits at (i / chpad)·world·chpad + r·chpad + i % chpad.  world = 1: nch = 1 and
-  // the position is i.  prows() = nch·world·chpad rows.
-  int nch = 1, world = 1;
-  int64_t chpad = 0;
-  int64_t own0 = 0, own_n = 0;   // this rank's dense row range
-  // dst CSR of this side restricted to own rows (local row index; col = padded src position)
-  DevBuf d_ptr, d_col, d_val;
-  int64_t own_nnz = 0;
-  std::vector<int64_t> h_deg;    // degree per own row
-  DevBuf d_rows;                 // own local rows grouped by bucket
-  DevBuf d_desc;                 // int4 per d_rows entry: {row, p0 lo, p0 hi, degree} (light16 prefetch)
-  int64_t boff[NBUCKET + 1] = {0};
-  int64_t bnnz[NBUCKET] = {0};
-  float vmax = 0.f;              // max |rating| over own dst rows (heavy-build fp16 scaling)
-  float vmin = 0.f;              // min |rating| over own dst rows: vmin == vmax -> one confidence c
-  DevBuf d_X;                    // [own_n][KP] factors in basis B
-  DevBuf d_Z;                    // [prows][KP] rotated factors (src role), gathered layout
-  DevBuf d_Xfull;                // world > 1: [prows][KP] every rank's X (basis B), gathered layout
-  bool full_valid = false;       // d_Xfull holds the current X (gathered behind the solve on st2)
-  int64_t prows() const { return (int64_t)nch * world * chpad; }
-  int64_t pos(int r, int64_t i) const { return (i / chpad) * world * chpad + (int64_t)r * chpad + i % chpad; }
-  DevBuf d_B;                    // fp64 [KP][KP] orthogonal basis on the device: original = X · Bᵀ
-  DevBuf d_Gk;                   // fp64 [KP][KP] last Gram of this side (as src), in basis d_GB
-  DevBuf d_GB;                   // fp64 [KP][KP] the side's basis when d_Gk was computed (G_orig = GB G GBᵀ)
-  bool has_gram = false;
-  bool has_factors = false;
-  double t[ALS_T_COUNT] = {0};
-  int64_t stats[4] = {0};
-  int64_t solver[4] = {0};       // NNLS iterations: sum over rows, max, rows (last half-sweep)
-  DevBuf d_orig;                 // [n][KP] original-basis factors, dense order (materialised)
-  bool orig_valid = false;
-  // split-K of the heavy tail: the first n_split heavy rows (degree > split chunk), their chunks
-  int64_t n_split = 0, n_chunks = 0;
-  DevBuf d_chunk_row, d_chunk_idx, d_slot0;
-  // nonnegative: the first n_batch rows of the (degree-ascending) light list go to the lockstep
-  // NNLS kernel, rows [bat_off[v], bat_off[v+1]) with BATCH_SLOTS[v] slots per workgroup
-  int64_t n_batch = 0, n_batch_nnz = 0;
-  int64_t bat_off[6] = {0};
-  // solve chunks (world > 1, Cholesky path): chunk q's rows of bucket b are the list positions
-  // [cb[b][q], cb[b][q + 1]); its split-K rows are the first split_n[q] of its heavy segment, their
-  // chunk lists start at ck_off[q] and their (chunk-local) slot0 at sl_off[q]
-  int nsolve = 1;
-  int64_t cb[NBUCKET][9] = {{0}};
-  int64_t c8[8] = {0};           // bucket B_L16, solve chunk q: its first c8[q] rows have degree <= 8 (paired)
-  int64_t split_n[8] = {0}, ck_off[9] = {0}, sl_off[8] = {0};
-};
-
-}  // namespace
-
-struct als_ctx {
-  als_params p{};
-  int KP = 0;
-  int dev = 0;
-  hipStream_t st = nullptr;
-  int rank = 0, world = 1;
-  ncclComm_t comm = nullptr;
-  // host transport (tests: several processes sharing one GPU exchange through the host)
-  int (*h_allreduce)(void*, double*, int64_t) = nullptr;
-  int (*h_allgather)(void*, float*, int64_t) = nullptr;
-  void* h_user = nullptr;
-  Side s[2];
-  int64_t nnz = 0;
-  bool has_ratings = false;
-  bool model_only = false;
-  DevBuf slab, d_G, d_P, d_lam, d_err, d_Gt, d_cs, d_csmax;
-  DevBuf d_eig;                  // device eigensolver scratch (eig.hip)
-  DevBuf d_partial, d_reduced;   // split-K partial / reduced A' records (shared by both sides)
-  DevBuf d_Zhl;                  // pre-split src rows of the uniform-confidence heavy build
-  DevBuf d_Pf;                   // P's bf16 parts in MFMA fragment order (rotate_bf)
-  DevBuf d_iters;                // NNLS iteration counters (sum, max)
-  DevBuf d_gfrag, d_counter;     // lockstep NNLS: G in MFMA operand order, row counter
-  int n_cu = 256;
-  // top-k counters, cumulative: [0] rows through the MFMA scan, [1] rows re-scored by the exact scan
-  // (certification misses), [2] dst chunks scanned, [3] dst chunks a full scan would take
-  int64_t topk_stats[4] = {0, 0, 0, 0};
-  // top-k device time, cumulative (ms, HIP events on st): [0] order + mask, [1] MFMA scan, [2] select,
-  // [3] exact rescans; [4] scan flops (2·KP per src x dst pair the scan's waves scored)
-  double topk_ms[5] = {0, 0, 0, 0, 0};
-  hipEvent_t evt[5] = {};
-  // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
-  // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was
-  // rescanned when d_last_need[p] != 0; its src row is p (last_rows_dense) or last_rows[p]
-  mutable std::vector<int32_t> last_rescan;
-  DevBuf d_last_need;
-  double* h_plan = nullptr;      // pinned: the top-k plan's dst Gram [KP][KP] + two max row norms
-  int64_t last_need_n = 0;
-  std::vector<int32_t> last_rows;
-  mutable bool last_rescan_ready = true;
-  bool last_rows_dense = false;
-  int last_src = 0;
-  int split_len = 0;             // ratings per split-K chunk (0: no split)
-  int slab_blocks = 0;
-  hipEvent_t ev[8] = {};
-  hipStream_t st2 = nullptr;     // world > 1: factor-chunk gathers behind the solve
-  // als_fork: a fork views its parent's ingest buffers; the parent is freed after its last fork
-  als_ctx* parent = nullptr;
-  int forks = 0;
-  bool doomed = false;
-  hipEvent_t evc[9] = {};        // per solve chunk: done on st; [8]: gathers done on st2
-};
-
-namespace {
-
-int set_device(als_ctx* c) {
+int albedo::set_device(als_ctx* c) {
   HIPCHK(hipSetDevice(c->dev));
   return ALS_OK;
 }
@@ -212,11 +61,14 @@ int set_device(als_ctx* c) {
 // stream, so a plain hipMemcpy / hipMemset could overlap the engine's kernels (a host-to-device
 // hipMemcpy from pageable memory may return before its DMA lands, a device-to-device one does not
 // wait at all, and neither waits for kernels still running on c->st).
-hipError_t copy_st(const als_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+hipError_t albedo::copy_st(const als_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   if (bytes == 0) return hipSuccess;
   const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->st);
   return e != hipSuccess ? e : hipStreamSynchronize(c->st);
 }
+
+namespace {
+
 hipError_t fill_st(const als_ctx* c, void* dst, int v, size_t bytes) {
   if (bytes == 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(dst, v, bytes, c->st);
@@ -301,9 +153,11 @@ int allgather_rows(als_ctx* c, float* buf, int64_t rows_per_rank, hipStream_t s)
   return ALS_OK;
 }
 
+}  // namespace
+
 // all-gather of host blocks: buf holds world blocks of n floats (this rank's filled); bytes are
 // moved, never combined (ids travel as float bit patterns)
-int allgather_host(als_ctx* c, float* buf, int64_t n) {
+int albedo::allgather_host(als_ctx* c, float* buf, int64_t n) {
   if (c->world == 1) return ALS_OK;
   if (c->comm) {
     DevBuf d;
@@ -318,6 +172,8 @@ int allgather_host(als_ctx* c, float* buf, int64_t n) {
   if (c->h_allgather(c->h_user, buf, n) != 0) return fail(ALS_E_RCCL, "host all-gather callback failed");
   return ALS_OK;
 }
+
+namespace {
 
 // Gathers layout chunks [q0, q1) of the own rows `own` ([nch·chpad][KP], zero past own_n) into
 // `full` ([prows][KP]) on stream s: chunk q of every rank is one contiguous all-gather.
@@ -673,11 +529,15 @@ std::string err_paths(int err) {
   return r;
 }
 
-float event_ms(hipEvent_t a, hipEvent_t b) {
+}  // namespace
+
+float albedo::event_ms(hipEvent_t a, hipEvent_t b) {
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, a, b);
   return ms;
 }
+
+namespace {
 
 // fp16 column scales of the heavy build for dst side T over the gathered src rows Z
 // have_max: the rotation left the column maxima of Z in d_csmax (rotate_kernel's epilogue)
@@ -1112,8 +972,10 @@ int half_sweep(als_ctx* c, int t) {
   return ALS_OK;
 }
 
+}  // namespace
+
 // original-basis factors of `side`, dense order, on device: d_orig [n][KP]
-int materialize(als_ctx* c, int side) {
+int albedo::materialize(als_ctx* c, int side) {
   Side& S = c->s[side];
   if (S.orig_valid) return ALS_OK;
   if (!S.has_factors) return fail(ALS_E_STATE, "factors are not available (call fit first)");
@@ -1147,13 +1009,11 @@ int materialize(als_ctx* c, int side) {
   return ALS_OK;
 }
 
-int64_t find_row(const Side& S, int32_t id) {
+int64_t albedo::find_row(const Side& S, int32_t id) {
   auto it = std::lower_bound(S.ids.begin(), S.ids.end(), id);
   if (it == S.ids.end() || *it != id) return -1;
   return it - S.ids.begin();
 }
-
-}  // namespace
 
 // ================================================================================================
 // C ABI
@@ -1603,799 +1463,6 @@ int als_model_create(int32_t rank, int64_t nu, const int32_t* uids, const float*
   return ALS_OK;
 }
 
-// One recommendForAll* call's prepared dst side (topk.hip): max row norms (the pre-selection's error
-// bound), fp16 power-of-two scales, the descending-norm fp16 image with chunk head norms, dst ids on
-// the device; plus the per-chunk scratch reused by every src chunk.
-struct TopkPlan {
-  int src = 0, k = 0;
-  bool exact_only = false;
-  double tmax = 0.0, smax = 0.0, ssc = 1.0, tsc = 1.0;
-  int CH = 0;
-  int64_t n_chunks = 0, n_super = 0;
-  bool prune = false;
-  DevBuf d_th, d_keys, d_perm, d_nperm, d_tp, d_tmp, d_dstids, d_VP, d_cfeat, d_supf, d_probe, d_slab, d_G;
-  DevBuf d_scan;
-  // a pass's device buffers; two sets, so that a pass's select / rescans (on the post stream) can run
-  // while the next pass orders and scans with the other set (r06)
-  struct PassBufs {
-    DevBuf d_src, d_ls, d_lc, d_flag, d_okeys, d_order, d_srcs, d_otmp, d_thr, d_sf, d_mask, d_kth, d_inv;
-    DevBuf d_cnt;  // int [4]: the range's flagged count, the rescan work counter, the set's flagged total
-  } pb[2];
-  // per call (topk_begin .. topk_finish): the passes run back to back with no host round trip; their
-  // event pairs, scan counters (d_scan[pass]) and rows per scan workgroup are read at the end
-  // per pass: start, order + mask done, scan done, then per output range: select done, rescans done
-  std::vector<hipEvent_t> evs;
-  struct PassRec { int rpw; size_t e0; int ranges; };
-  std::vector<PassRec> passes;
-  int64_t n_passes = 0;
-  hipError_t event(size_t i, hipEvent_t* e) {  // the i-th event of the pool (created on demand)
-    while (evs.size() <= i) {
-      hipEvent_t x;
-      const hipError_t r = hipEventCreate(&x);
-      if (r != hipSuccess) return r;
-      evs.push_back(x);
-    }
-    *e = evs[i];
-    return hipSuccess;
-  }
-  ~TopkPlan() {
-    for (hipEvent_t e : evs)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
-// The dst side's Gram Σ t tᵀ (original basis) on the device, copied into c->h_plan ([KP][KP] fp64)
-// on st; `done` is recorded behind the copy, so the host can wait for it alone.
-int topk_dst_gram(als_ctx* c, const Side& T, TopkPlan& P, hipEvent_t done) {
-  const int KP = c->KP;
-  const int nblk = gram_slab_blocks(KP, T.n);
-  double* slab = c->slab.as<double>();  // the sweeps' Gram scratch (idle here, same stream) when it fits
-  if (c->slab_blocks < nblk || !slab) {
-    HIPCHK(P.d_slab.ensure(gram_slab_doubles(KP, nblk) * 8));
-    slab = P.d_slab.as<double>();
-  }
-  HIPCHK(P.d_G.ensure((size_t)KP * KP * 8));
-  HIPCHK(launch_gram(KP, T.d_orig.as<float>(), T.n, slab, nblk, P.d_G.as<double>(), c->st));
-  // into pinned memory: a pageable copy would block the host here until the stream drains
-  HIPCHK(hipMemcpyAsync(c->h_plan, P.d_G.p, (size_t)KP * KP * 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipEventRecord(done, c->st));
-  return ALS_OK;
-}
-
-// The leading TOPK_M eigenvectors of that Gram, fp64 [TOPK_M][KP]: the directions the top-k chunk
-// bound keeps exactly (topk.hip).  Runs on the host while the row norms are computed on the device.
-int topk_dst_basis(als_ctx* c, const double* Gf, std::vector<double>& VP) {
-  const int KP = c->KP, k = c->p.rank;
-  std::vector<double> Gk((size_t)k * k), w(k), V((size_t)k * k);
-  for (int i = 0; i < k; ++i)
-    for (int j = 0; j < k; ++j) Gk[(size_t)i * k + j] = Gf[(size_t)i * KP + j];
-  if (!sym_eig(k, Gk.data(), w.data(), V.data()))
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
-                "the dst Gram matrix is not finite (row norms above ~2^63) or its eigendecomposition did not converge");
-  std::vector<int> idx(k);
-  std::iota(idx.begin(), idx.end(), 0);
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return w[a] > w[b]; });
-  VP.assign((size_t)TOPK_M * KP, 0.0);
-  for (int d = 0; d < TOPK_M && d < k; ++d)
-    for (int i = 0; i < k; ++i) VP[(size_t)d * KP + i] = V[(size_t)i * k + idx[d]];
-  return ALS_OK;
-}
-
-// The scan prunes against the kt-th best candidate so far, not the 64th: certification needs a gap
-// between the k-th exact score and the kt-th approximate one (~1e-3 relative), and k + 16 leaves one
-// while the threshold rises faster than at 64 (fewer dst chunks scanned once the factors converge).
-// The lists still hold 64 and the best 64 are rescored.
-// the running threshold's rank in the candidate lists: k + 16 (c4 all users after 25 sweeps: k + 8 /
-// 12 / 16 / 24 -> 33.6 / 47.6 / 50.7 / 46.9M users/s; fewer leave more rows to the exact rescan)
-int topk_threshold_rank(int k) { return std::max(k, std::min(TOPK_KC, k + ALBEDO_TOPK_KT_EXTRA)); }
-
-int topk_plan(als_ctx* c, int src, int k, TopkPlan& P, const std::function<void(const char*)>& stamp = nullptr) {
-  auto st = [&](const char* w) {
-    if (stamp) stamp(w);
-  };
-  P.src = src;
-  P.k = k;
-  P.exact_only = k > TOPK_KC;  // no MFMA pre-selection: exact full scan of every row
-  TRYC(materialize(c, src));
-  TRYC(materialize(c, 1 - src));
-  st("  plan: materialize dst");
-  Side& S = c->s[src];
-  Side& T = c->s[1 - src];
-  const int KP = c->KP;
-  // the dst Gram first; its host eigensolve overlaps the row-norm launches behind it
-  std::vector<double> VP;
-  hipEvent_t ev_gram;
-  HIPCHK(P.event(0, &ev_gram));
-  if (!c->h_plan) HIPCHK(hipHostMalloc((void**)&c->h_plan, ((size_t)KP * KP + 2) * 8, hipHostMallocDefault));
-  {
-    DevBuf d_nrm;
-    HIPCHK(d_nrm.ensure(16));
-    TRYC(topk_dst_gram(c, T, P, ev_gram));
-    HIPCHK(launch_rownorm_max(T.d_orig.as<float>(), T.n, KP, c->p.rank, d_nrm.as<unsigned long long>(), c->st));
-    HIPCHK(launch_rownorm_max(S.d_orig.as<float>(), S.n, KP, c->p.rank, d_nrm.as<unsigned long long>() + 1, c->st));
-    double* nr = c->h_plan + (size_t)KP * KP;
-    HIPCHK(hipMemcpyAsync(nr, d_nrm.p, 16, hipMemcpyDeviceToHost, c->st));
-    st("  plan: dst Gram + row norms enqueued");
-    HIPCHK(hipEventSynchronize(ev_gram));
-    st("  plan: dst Gram");
-    TRYC(topk_dst_basis(c, c->h_plan, VP));
-    st("  plan: host eigensolve (row norms on the device)");
-    HIPCHK(hipStreamSynchronize(c->st));
-    P.tmax = nr[0];
-    P.smax = nr[1];
-  }
-  // |entry| <= row norm, so scaling by 2^(13 - ceil(log2 max norm)) keeps every fp16 value < 2^13
-  auto pow2_scale = [](double m) {
-    if (!(m > 0.0) || !std::isfinite(m)) return 1.0;
-    int e = 0;
-    std::frexp(m, &e);  // m < 2^e
-    e = std::max(-60, std::min(60, 13 - e));
-    return std::ldexp(1.0, e);
-  };
-  P.ssc = pow2_scale(P.smax);
-  P.tsc = pow2_scale(P.tmax);
-  // dst side in descending-norm order, fp16 rows + chunk head norms (also for k > 64: the exact scan
-  // visits the dst rows in this norm order and stops early)
-  P.CH = topk_chunk_rows(KP);
-  P.n_chunks = (T.n + P.CH - 1) / P.CH;
-  P.n_super = (P.n_chunks + TOPK_SUPER - 1) / TOPK_SUPER;
-  // the chunk bound prunes only catalogues larger than the candidate lists (smaller ones are scanned
-  // whole: the lists then hold every dst row, which select's n_dst <= TOPK_KC shortcut relies on)
-  P.prune = T.n > TOPK_KC;
-  st("  plan: row norms");
-  HIPCHK(P.d_VP.ensure(VP.size() * 8));
-  HIPCHK(hipMemcpyAsync(P.d_VP.p, VP.data(), VP.size() * 8, hipMemcpyHostToDevice, c->st));
-  const int64_t nn = std::max<int64_t>(T.n, 1);
-  HIPCHK(P.d_th.ensure((size_t)std::max<int64_t>(P.n_chunks, 1) * P.CH * KP * 2));
-  HIPCHK(P.d_keys.ensure((size_t)nn * 16));
-  HIPCHK(P.d_perm.ensure((size_t)nn * 8));
-  HIPCHK(P.d_nperm.ensure((size_t)nn * 8));
-  HIPCHK(P.d_tp.ensure((size_t)nn * TOPK_M * 8));
-  HIPCHK(P.d_cfeat.ensure((size_t)std::max<int64_t>(P.n_chunks, 1) * TOPK_CF * 4));
-  HIPCHK(P.d_supf.ensure((size_t)std::max<int64_t>(P.n_super, 1) * TOPK_CF * 4));
-  HIPCHK(P.d_probe.ensure((size_t)TOPK_NPROBE * KP * 2));
-  const size_t tb = topk_sort_temp_bytes(T.n);
-  HIPCHK(P.d_tmp.ensure(std::max<size_t>(tb, 16)));
-  if (T.n > 0)
-    HIPCHK(topk_prepare(KP, c->p.rank, T.d_orig.as<float>(), T.n, (float)P.tsc, P.d_VP.as<double>(), P.d_tmp.p, tb,
-                        P.d_keys.as<uint32_t>(), P.d_perm.as<uint32_t>(), P.d_nperm.as<uint32_t>(),
-                        P.d_tp.as<double>(), P.d_th.p, P.d_cfeat.as<float>(), P.d_supf.as<float>(), P.d_probe.p,
-                        c->st));
-  st("  plan: dst sort + fp16 pack + chunk features");
-  HIPCHK(P.d_dstids.ensure(std::max<int64_t>(T.n, 1) * 4));
-  HIPCHK(hipMemcpyAsync(P.d_dstids.p, T.ids.data(), T.n * 4, hipMemcpyHostToDevice, c->st));
-  HIPCHK(P.d_scan.ensure(8));
-  st("  plan: dst ids");
-  return ALS_OK;
-}
-
-// Src rows per top-k pass: 2^25 (candidate lists 32 GiB of the 288 GB), or what half of the free
-// device memory holds at ~1.5 KiB per src row (the TOPK_CAP-entry candidate list plus the row's
-// features, order keys and output slots), so a smaller GPU or ranks sharing one fall back to more passes
-static int64_t topk_pass_rows(als_ctx* c) {
-  size_t fr = 0, tot = 0;
-  int64_t cap = (int64_t)1 << 25;
-  if (set_device(c) == ALS_OK && hipMemGetInfo(&fr, &tot) == hipSuccess) {
-    const int64_t fit = (int64_t)(fr / 2 / 1536);
-    cap = std::min<int64_t>(cap, std::max<int64_t>((int64_t)1 << 16, fit & ~(int64_t)0xFFFF));
-  }
-  return cap;
-}
-
-// A call's top-k passes: topk_begin (n_rows positions, at most n_passes passes; the rescan flags of
-// position p land in c->d_last_need[p]), topk_run_rows per pass, topk_finish (one synchronisation:
-// timers and counters).
-int topk_begin(als_ctx* c, TopkPlan& P, int64_t n_rows, int64_t n_passes, const int32_t* rows) {
-  HIPCHK(P.d_scan.ensure((size_t)std::max<int64_t>(n_passes, 1) * 8));
-  HIPCHK(hipMemsetAsync(P.d_scan.p, 0, (size_t)std::max<int64_t>(n_passes, 1) * 8, c->st));
-  for (auto& B : P.pb) {
-    HIPCHK(B.d_cnt.ensure(16));
-    HIPCHK(hipMemsetAsync(B.d_cnt.p, 0, 16, c->st));
-  }
-  HIPCHK(c->d_last_need.ensure((size_t)std::max<int64_t>(n_rows, 1) * 4));
-  HIPCHK(hipMemsetAsync(c->d_last_need.p, 0, (size_t)std::max<int64_t>(n_rows, 1) * 4, c->st));
-  c->last_need_n = n_rows;
-  c->last_src = P.src;
-  c->last_rows_dense = rows == nullptr;
-  if (rows) c->last_rows.assign(rows, rows + n_rows);
-  else c->last_rows.clear();
-  c->last_rescan.clear();
-  c->last_rescan_ready = false;
-  P.n_passes = n_passes;
-  P.passes.clear();
-  return ALS_OK;
-}
-
-int topk_finish(als_ctx* c, TopkPlan& P, hipStream_t sp = nullptr) {
-  if (sp) HIPCHK(hipStreamSynchronize(sp));
-  HIPCHK(hipStreamSynchronize(c->st));
-  const int64_t np = (int64_t)P.passes.size();
-  std::vector<unsigned long long> scanned((size_t)std::max<int64_t>(np, 1), 0ull);
-  int cnt[4] = {0, 0, 0, 0}, cnt1[4] = {0, 0, 0, 0};
-  if (np > 0) HIPCHK(copy_st(c, scanned.data(), P.d_scan.p, np * 8, hipMemcpyDeviceToHost));
-  HIPCHK(copy_st(c, cnt, P.pb[0].d_cnt.p, 16, hipMemcpyDeviceToHost));
-  HIPCHK(copy_st(c, cnt1, P.pb[1].d_cnt.p, 16, hipMemcpyDeviceToHost));
-  cnt[2] += cnt1[2];
-  for (int64_t q = 0; q < np; ++q) {
-    const TopkPlan::PassRec& R = P.passes[q];
-    const hipEvent_t* e = P.evs.data() + R.e0;
-    c->topk_ms[0] += event_ms(e[0], e[1]);
-    c->topk_ms[1] += event_ms(e[1], e[2]);
-    for (int r = 0; r < R.ranges; ++r) {
-      c->topk_ms[2] += event_ms(r == 0 ? e[2] : e[3 + 2 * r - 1], e[3 + 2 * r]);
-      c->topk_ms[3] += event_ms(e[3 + 2 * r], e[4 + 2 * r]);
-    }
-    c->topk_stats[2] += (int64_t)scanned[q];
-    c->topk_ms[4] += (double)scanned[q] * (R.rpw / 4) * 2.0 * c->KP;  // per wave: rpw / 4 src rows x each dst row
-  }
-  c->topk_stats[1] += cnt[2];
-  return ALS_OK;
-}
-
-// One pass: the nc src rows `rows` (host, dense row indices; nullptr: rows row0 .. row0 + nc - 1,
-// generated on the device) at positions pos0 .. pos0 + nc - 1 of the call, into the device lists
-// d_oid / d_osc ([nc][k], score desc, id asc).  Rows that fail certification are compacted on the
-// device and re-scored by a persistent exact scan in the same stream: nothing here waits for the GPU.
-// After the scan the results are finished in output ranges of `range` rows (select, then the
-// rescans of the range); ready(o0, o1), when given, is called once a range's work is enqueued, so
-// the caller can copy those rows out while the next range computes.
-using TopkReady = std::function<int(int64_t, int64_t)>;
-int topk_run_rows(als_ctx* c, TopkPlan& P, const int32_t* rows, int64_t row0, int64_t pos0, int64_t nc, int32_t* d_oid,
-                  float* d_osc, int64_t range = INT64_MAX, const TopkReady& ready = nullptr, int par = 0,
-                  hipStream_t sp = nullptr) {
-  // buffer set `par`; with a post stream sp the select / rescans wait for the scan on sp, so the
-  // caller's next pass (the other set) can order and scan meanwhile
-  TopkPlan::PassBufs& B = P.pb[par];
-  hipStream_t ps = sp ? sp : c->st;
-  Side& S = c->s[P.src];
-  Side& T = c->s[1 - P.src];
-  const int KP = c->KP, k = P.k;
-  if (nc <= 0) return ALS_OK;
-  HIPCHK(B.d_src.ensure(nc * 4));
-  if (!P.exact_only) {
-    HIPCHK(B.d_ls.ensure(nc * TOPK_CAP * 8));
-    HIPCHK(B.d_lc.ensure(nc * 4));
-  }
-  if (rows) HIPCHK(hipMemcpyAsync(B.d_src.p, rows, nc * 4, hipMemcpyHostToDevice, c->st));
-  else HIPCHK(launch_iota_i32(B.d_src.as<int32_t>(), nc, row0, c->st));
-  (void)S;
-  TopkArgs a{};
-  a.S = S.d_orig.as<float>();
-  a.T = T.d_orig.as<float>();
-  a.src_rows = B.d_src.as<int32_t>();
-  a.n_src = nc;
-  a.n_dst = T.n;
-  a.dst_ids = P.d_dstids.as<int32_t>();
-  a.kreal = c->p.rank;
-  a.k = k;
-  a.kt = topk_threshold_rank(k);
-  a.tmax_norm = (float)(P.tmax * (1.0 + 1e-6));
-  a.Th = P.d_th.p;
-  a.perm = P.d_perm.as<uint32_t>();
-  a.n_chunks = P.n_chunks;
-  a.VP = P.d_VP.as<double>();
-  a.cfeat = P.prune ? P.d_cfeat.as<float>() : nullptr;
-  a.probe = P.d_probe.p;
-  a.ssc = (float)P.ssc;
-  a.tsc = (float)P.tsc;
-  a.unscale = (float)(1.0 / (P.ssc * P.tsc));
-  a.scaled = (float)(P.ssc * P.tsc);
-  a.lent = B.d_ls.as<uint2>();
-  a.lcnt = B.d_lc.as<int32_t>();
-  // scan order: 12 bits of depth, then 7 / 7 / 6 bits of direction (topk_order_key_kernel; c4 all
-  // users: scan 260 -> 193 ms, order + mask 56 -> 39 ms against the depth-only key; 18 / 22 / 24
-  // direction bits 206 / 206 / 276 ms, other splits of 20 the same 193)
-  a.order_dir_bits = 7 | (7 << 8) | (6 << 16);
-  a.out_ids = d_oid;
-  a.out_scores = d_osc;
-  int32_t* d_need = c->d_last_need.as<int32_t>() + pos0;
-  a.need_exact = d_need;
-  if (!P.exact_only) {
-    HIPCHK(B.d_kth.ensure(nc * 4));
-    a.kth0 = B.d_kth.as<float>();
-  }
-  const int64_t pass = (int64_t)P.passes.size();
-  if (pass >= P.n_passes) return fail(ALS_E_STATE, "top-k: more passes than planned");
-  a.scanned = P.d_scan.as<unsigned long long>() + pass;
-  if (P.exact_only) {
-    HIPCHK(launch_topk_exact(KP, a, nullptr, nc, c->st));
-    if (ready) TRYC(ready(0, nc));
-    return ALS_OK;
-  }
-  const int64_t nr = std::max<int64_t>(1, (nc + range - 1) / range);  // output ranges
-  const size_t e0 = P.evs.size();
-  hipEvent_t ev[3];
-  for (int i = 0; i < 3; ++i) HIPCHK(P.event(e0 + i, &ev[i]));
-  // scan order: rows that stop at similar depths share a workgroup (topk_order); the select writes
-  // each row's results back to its own slot
-  TopkArgs b = a;
-  HIPCHK(hipEventRecord(ev[0], c->st));
-  HIPCHK(B.d_okeys.ensure(nc * 8));
-  HIPCHK(B.d_order.ensure(nc * 8));
-  HIPCHK(B.d_srcs.ensure(nc * 4));
-  const size_t otb = topk_order_temp_bytes(nc);
-  HIPCHK(B.d_otmp.ensure(std::max<size_t>(otb, 16)));
-  HIPCHK(B.d_thr.ensure(nc * 8));
-  HIPCHK(B.d_sf.ensure((size_t)nc * TOPK_SF * 8));
-  float* sf_tmp = B.d_sf.as<float>();
-  float* sf_sorted = sf_tmp + (size_t)nc * TOPK_SF;
-  HIPCHK(topk_order(KP, a, B.d_otmp.p, otb, B.d_okeys.as<uint32_t>(), B.d_order.as<uint32_t>(), B.d_srcs.as<int32_t>(),
-                    B.d_thr.as<float>(), B.d_thr.as<float>() + nc, sf_tmp, sf_sorted, c->st));
-  b.src_rows = B.d_srcs.as<int32_t>();
-  b.out_pos = B.d_order.as<uint32_t>();
-  b.thr0 = B.d_thr.as<float>() + nc;
-  b.sfeat = sf_sorted;
-  const int rpw = topk_rows_per_workgroup(KP, nc, c->n_cu);
-  if (P.prune) {  // per scan workgroup, the chunks its rows can need against the starting thresholds
-    const int64_t n_wg = (nc + rpw - 1) / rpw;
-    b.mask_words = (P.n_super + 1) / 2;
-    HIPCHK(B.d_mask.ensure((size_t)n_wg * b.mask_words * 4));
-    b.mask = B.d_mask.as<uint32_t>();
-    HIPCHK(launch_topk_mask(b, rpw, P.d_supf.as<float>(), P.n_super, B.d_mask.as<uint32_t>(), c->st));
-  }
-  HIPCHK(hipEventRecord(ev[1], c->st));
-  HIPCHK(launch_topk(KP, b, c->n_cu, c->st));
-  HIPCHK(hipEventRecord(ev[2], c->st));
-  HIPCHK(B.d_flag.ensure(nc * 4));
-  if (nr > 1) HIPCHK(B.d_inv.ensure(nc * 4));
-  if (sp) HIPCHK(hipStreamWaitEvent(sp, ev[2], 0));  // the select needs this pass's scan
-  if (nr > 1) {  // select by output slot: slot -> scan position
-    HIPCHK(launch_invert_perm(b.out_pos, nc, B.d_inv.as<uint32_t>(), ps));
-  }
-  P.passes.push_back(TopkPlan::PassRec{rpw, e0, 0});
-  for (int64_t r = 0; r < nr; ++r) {
-    const int64_t o0 = r * range, n = std::min<int64_t>(range, nc - o0);
-    hipEvent_t es, ex;
-    HIPCHK(P.event(e0 + 3 + 2 * r, &es));
-    HIPCHK(P.event(e0 + 4 + 2 * r, &ex));
-    TopkArgs bs = b;
-    if (nr > 1) {
-      bs.in_pos = B.d_inv.as<uint32_t>();
-      bs.slot0 = o0;
-      bs.n_slots = n;
-    }
-    HIPCHK(launch_topk_select(KP, bs, ps));
-    HIPCHK(hipEventRecord(es, ps));
-    // certification failures of the range: compacted on the device (range-local positions), re-scored
-    // in place
-    TopkArgs ar = a;
-    ar.src_rows = a.src_rows + o0;
-    ar.out_ids = a.out_ids + o0 * k;
-    ar.out_scores = a.out_scores + o0 * k;
-    ar.kth0 = a.kth0 + o0;
-    ar.n_src = n;
-    HIPCHK(hipMemsetAsync(B.d_cnt.p, 0, 8, ps));  // this range's count and work counter
-    HIPCHK(launch_topk_exact_flagged(KP, ar, d_need + o0, n, B.d_flag.as<int32_t>(), B.d_cnt.as<int>(), c->n_cu, ps));
-    HIPCHK(hipEventRecord(ex, ps));
-    P.passes.back().ranges = (int)(r + 1);
-    if (ready) TRYC(ready(o0, o0 + n));
-  }
-  c->topk_stats[0] += nc;
-  c->topk_stats[3] += (nc + rpw - 1) / rpw * 4 * P.n_chunks * P.CH;  // dst rows x waves
-  return ALS_OK;
-}
-
-int als_recommend(als_ctx* c, int side, int32_t k, const int32_t* subset, int64_t n_subset, int32_t* src_ids_out,
-                  int32_t* dst_ids_out, float* scores_out) {
-  if (!c || (side != 0 && side != 1) || !dst_ids_out || !scores_out)
-    return fail(ALS_E_INVALID_ARGUMENT, "bad args");
-  if (k <= 0) return fail(ALS_E_INVALID_ARGUMENT, "num must be positive");
-  if (k > TOPK_MAX)
-    return fail(ALS_E_UNSUPPORTED, "num above " + std::to_string(TOPK_MAX) + " is not supported by this engine");
-  TRYC(set_device(c));
-  // ALBEDO_TOPK_TRACE (diagnostic): wall-clock stamps of the call's phases on stderr, the stream
-  // synchronised at each (so the stamps bracket device work)
-  static const bool trace = [] {
-    const char* e = std::getenv("ALBEDO_TOPK_TRACE");
-    return e && *e && *e != '0';
-  }();
-  const auto t_start = std::chrono::steady_clock::now();
-  auto stamp = [&](const char* what) {
-    if (!trace) return;
-    (void)hipStreamSynchronize(c->st);
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    std::fprintf(stderr, "[topk] %9.2f ms  %s\n", ms, what);
-  };
-  const int src = side;
-  TRYC(materialize(c, src));
-  stamp("materialize src");
-  Side& S = c->s[src];
-  const Side& T = c->s[1 - src];
-  const int64_t nq = subset ? n_subset : S.n;
-  // recommendForAll*: every src row, in row order -- no host index arrays (the device generates the
-  // row indices of each pass); a subset: id -> row by a merge walk when ascending (the usual case),
-  // binary search otherwise, unknown ids padded here
-  const bool all_rows = subset == nullptr;
-  std::vector<int32_t> known;
-  std::vector<int64_t> pos;
-  if (!all_rows) {
-    std::vector<int32_t> qrow(nq);
-    if (std::is_sorted(subset, subset + nq)) {
-      int64_t r = 0;
-      for (int64_t i = 0; i < nq; ++i) {
-        while (r < S.n && S.ids[r] < subset[i]) ++r;
-        qrow[i] = (r < S.n && S.ids[r] == subset[i]) ? (int32_t)r : -1;
-      }
-    } else {
-      for (int64_t i = 0; i < nq; ++i) qrow[i] = (int32_t)find_row(S, subset[i]);
-    }
-    known.reserve(nq);
-    pos.reserve(nq);
-    for (int64_t i = 0; i < nq; ++i)
-      if (qrow[i] >= 0) {
-        known.push_back(qrow[i]);
-        pos.push_back(i);
-      } else {
-        std::fill(dst_ids_out + i * k, dst_ids_out + (i + 1) * k, -1);
-        std::fill(scores_out + i * k, scores_out + (i + 1) * k, NAN);
-      }
-  }
-  if (src_ids_out) {
-    if (all_rows) std::memcpy(src_ids_out, S.ids.data(), (size_t)nq * 4);
-    else std::memcpy(src_ids_out, subset, (size_t)nq * 4);
-  }
-  const int64_t n_known = all_rows ? nq : (int64_t)known.size();
-  auto posf = [&](int64_t i) { return all_rows ? i : pos[i]; };           // output slot of known row i
-  auto rowsf = [&](int64_t q0) { return all_rows ? nullptr : known.data() + q0; };  // null: rows q0 ..
-  const bool dense_out = n_known == nq;  // results land in place, no scatter
-  c->last_rescan.clear();
-  c->last_rescan_ready = true;
-  if (n_known == 0 || T.n == 0) return ALS_OK;
-  stamp("host id mapping");
-  // Src rows per pass: up to 2^25 (candidate lists 32 GiB of the 288 GB).  One scan launch over every
-  // row dispatches the heaviest workgroups (lowest relative thresholds) first and fills in behind
-  // them; split into 4M-row passes, each pass paid its own heavy tail (c4 all users: scan 436 ms in
-  // five passes, 260 ms in one; profiles/r05_bench_c4_topk_pass{4M,10M,20M}.json).  The results are
-  // finished and copied out in ranges of pass / 8 rows (at most 4M) while the next range computes.
-  // ALBEDO_TOPK_PASS (test knob): rows per pass.
-  // ALBEDO_TOPK_OVERLAP=1 (r06 experiment, off by default): with the lists written in place the select
-  // is link-bound (~40 GB/s of lists) and the scan compute-bound, so a call of >= 2M rows runs as two
-  // passes whose first select / rescans (post stream, second buffer set) overlap the second order +
-  // scan.  Measured slower (c4 all users 0.318 vs 0.293 s, profiles/r06_bench_c4_topk_overlap_REJECTED
-  // .json): the store-bound select waves slow the concurrent scan, and the second pass adds its own
-  // order, sort and mask.
-  const bool want_overlap = [] {
-    const char* e = std::getenv("ALBEDO_TOPK_OVERLAP");
-    return e && std::atoi(e) == 1;
-  }();
-  const int64_t chunk = [&] {
-    const char* e = std::getenv("ALBEDO_TOPK_PASS");
-    if (e && *e) return std::max<int64_t>(1 << 16, std::atoll(e));
-    const int64_t cap = topk_pass_rows(c);
-    const int64_t n_here = (std::min<int64_t>(n_known, ((int64_t)c->rank + 1) * ((n_known + c->world - 1) / c->world)) -
-                            std::min<int64_t>(n_known, (int64_t)c->rank * ((n_known + c->world - 1) / c->world)));
-    if (want_overlap && n_here >= ((int64_t)1 << 21)) return std::min<int64_t>(cap, (n_here + 1) / 2);
-    return cap;
-  }();
-  const int64_t range = std::min<int64_t>((int64_t)1 << 22, std::max<int64_t>(chunk / 8, 1 << 16));
-  // world > 1 (SURVEY §8(e) "Top-k: shard users"): rank r scores the r-th contiguous slice of the
-  // known src rows against the replicated dst factors; the lists are all-gathered afterwards
-  const int64_t per_rank = (n_known + c->world - 1) / c->world;
-  const int64_t lo = std::min<int64_t>(n_known, (int64_t)c->rank * per_rank);
-  const int64_t hi = std::min<int64_t>(n_known, lo + per_rank);
-  std::vector<int64_t> pstart;  // pass starts
-  {
-    int64_t q = lo;
-    while (hi - q > chunk) {
-      pstart.push_back(q);
-      q += chunk;
-    }
-    if (q < hi) {
-      pstart.push_back(q);
-    }
-  }
-  const int64_t n_pass = (int64_t)pstart.size();
-  // dense output (every row of the side, the recommendForAll* case): the caller's arrays are pinned
-  // in place (by a helper thread, while the plan runs) and each range's lists go down on a copy stream
-  // while the next range computes (two device buffers across passes); elsewise (or if pinning fails)
-  // each pass is copied back before the next starts
-  int pin_state = 0;  // bit 0: ids registered, bit 1: scores registered
-  const size_t pin_bytes = (size_t)(hi - lo) * k * 4;
-  // Zero-copy results (r06, default): the select / exact kernels write the lists straight into the
-  // mapped caller arrays over PCIe.  The DMA pipeline (device buffers, copies of each finished range
-  // on a copy stream) moved the 4.8 GB of an all-users c4 call at ~29 GB/s and finished ~110 ms after
-  // the last kernel; written in place, the select runs at the link's rate with nothing behind it.
-  // Mode 2 (default) selects in output-slot ranges, so a workgroup's four lists leave as one block of
-  // 16-B stores (c4 all users: DMA 0.339 s, mode 1 (scan order) 0.298-0.318 s, mode 2 0.291 s on the
-  // box that ran mode 1 at 0.318); ALBEDO_TOPK_ZEROCOPY=0: the DMA pipeline.
-  const int zmode = [] {
-    const char* e = std::getenv("ALBEDO_TOPK_ZEROCOPY");
-    return e ? std::atoi(e) : 2;
-  }();
-  bool zcopy = zmode == 1 || zmode == 2;
-  auto pin = [&, dev = c->dev]() {
-    if (hipSetDevice(dev) != hipSuccess) return;
-    const unsigned fl = zcopy ? hipHostRegisterMapped : hipHostRegisterDefault;
-    if (hipHostRegister(dst_ids_out + lo * k, pin_bytes, fl) != hipSuccess) return;
-    pin_state |= 1;
-    if (hipHostRegister(scores_out + lo * k, pin_bytes, fl) == hipSuccess) pin_state |= 2;
-  };
-  std::thread pin_thr;
-  const bool want_pin = dense_out && hi - lo > range;
-  if (want_pin) {
-    try {
-      pin_thr = std::thread(pin);
-    } catch (const std::system_error&) {
-      pin();  // no thread: pin here
-    }
-  }
-  TopkPlan P;
-  const int plan_rc = topk_plan(c, src, k, P, trace ? std::function<void(const char*)>(stamp) : nullptr);
-  if (pin_thr.joinable()) pin_thr.join();
-  (void)hipGetLastError();  // a refused registration is not an error: the synchronous path runs
-  if (pin_state == 1) (void)hipHostUnregister(dst_ids_out + lo * k);
-  bool async_out = pin_state == 3;
-  if (plan_rc != ALS_OK) {
-    if (async_out) {
-      (void)hipHostUnregister(dst_ids_out + lo * k);
-      (void)hipHostUnregister(scores_out + lo * k);
-    }
-    return plan_rc;
-  }
-  stamp("plan (materialize dst, Gram + host eig, dst sort + fp16 pack) + pin the output arrays");
-  int32_t* zids = nullptr;
-  float* zsc = nullptr;
-  if (async_out && zcopy) {
-    void* pi = nullptr;
-    void* ps = nullptr;
-    if (hipHostGetDevicePointer(&pi, dst_ids_out + lo * k, 0) == hipSuccess &&
-        hipHostGetDevicePointer(&ps, scores_out + lo * k, 0) == hipSuccess) {
-      zids = static_cast<int32_t*>(pi);
-      zsc = static_cast<float*>(ps);
-    } else {
-      zcopy = false;
-      (void)hipGetLastError();
-    }
-  }
-  hipStream_t cs = nullptr;
-  hipEvent_t ev_copy[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> ev_rng;  // one per finished range: the copy stream waits for it
-  DevBuf d_oid2[2], d_osc2[2];
-  // releases everything the async path holds (null-safe: also after a partial set-up)
-  hipStream_t sp = nullptr;                   // the post stream of overlapped passes (zero-copy)
-  hipEvent_t ev_post[2] = {nullptr, nullptr};  // buffer set b's last select / rescans are done
-  auto end_post = [&]() {
-    if (sp) (void)hipStreamSynchronize(sp);
-    for (auto& e : ev_post)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-    if (sp) (void)hipStreamDestroy(sp);
-    sp = nullptr;
-  };
-  auto end_async = [&]() {
-    end_post();
-    if (!async_out) return;
-    if (cs) (void)hipStreamSynchronize(cs);
-    (void)hipStreamSynchronize(c->st);
-    (void)hipHostUnregister(dst_ids_out + lo * k);
-    (void)hipHostUnregister(scores_out + lo * k);
-    for (int b = 0; b < 2; ++b) {
-      if (ev_copy[b]) (void)hipEventDestroy(ev_copy[b]);
-      ev_copy[b] = nullptr;
-    }
-    for (hipEvent_t e : ev_rng) (void)hipEventDestroy(e);
-    ev_rng.clear();
-    if (cs) (void)hipStreamDestroy(cs);
-    cs = nullptr;
-    async_out = false;
-  };
-  if (async_out) {  // the copy stream and its events; if any cannot be created, the synchronous path runs
-    bool ok = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) cs = nullptr;
-    for (int b = 0; b < 2 && ok; ++b)
-      if (!(ok = hipEventCreateWithFlags(&ev_copy[b], hipEventDisableTiming) == hipSuccess)) ev_copy[b] = nullptr;
-    if (!ok) {
-      end_async();
-      (void)hipGetLastError();
-    }
-  }
-  if (async_out && zcopy && n_pass > 1) {  // a failure here leaves the passes sequential
-    bool ok = hipStreamCreateWithFlags(&sp, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) sp = nullptr;
-    for (int b = 0; b < 2 && ok; ++b)
-      if (!(ok = hipEventCreateWithFlags(&ev_post[b], hipEventDisableTiming) == hipSuccess)) ev_post[b] = nullptr;
-    if (!ok) {
-      end_post();
-      (void)hipGetLastError();
-    }
-  }
-  DevBuf d_oid, d_osc;
-  {
-    const int rc = topk_begin(c, P, n_known, n_pass, all_rows ? nullptr : known.data());
-    if (rc != ALS_OK) {
-      end_async();
-      return rc;
-    }
-  }
-  for (int64_t it = 0; it < n_pass; ++it) {
-    const int64_t q0 = pstart[it], nc = (it + 1 < n_pass ? pstart[it + 1] : hi) - q0;
-    if (async_out && zcopy) {  // results written in place by the kernels
-      // mode 2: select in output-slot order by ranges (consecutive waves write consecutive lists);
-      // with a post stream, buffer set it & 1, reused once its previous select / rescans are done
-      const int par = sp ? (int)(it & 1) : 0;
-      int rc = ALS_OK;
-      if (sp && it >= 2 && hipStreamWaitEvent(c->st, ev_post[par], 0) != hipSuccess) rc = fail(ALS_E_HIP, "stream wait");
-      if (rc == ALS_OK)
-        rc = topk_run_rows(c, P, rowsf(q0), q0, q0, nc, zids + (q0 - lo) * k, zsc + (q0 - lo) * k,
-                           zmode == 2 ? range : INT64_MAX, nullptr, par, sp);
-      if (rc == ALS_OK && sp && hipEventRecord(ev_post[par], sp) != hipSuccess) rc = fail(ALS_E_HIP, "post event");
-      if (rc != ALS_OK) {
-        end_async();
-        return rc;
-      }
-      stamp("pass");
-      continue;
-    }
-    if (async_out) {
-      const int b = (int)(it & 1);
-      int rc = ALS_OK;
-      if (it >= 2 && hipStreamWaitEvent(c->st, ev_copy[b], 0) != hipSuccess) rc = fail(ALS_E_HIP, "stream wait");
-      if (rc == ALS_OK && (d_oid2[b].ensure(nc * k * 4) != hipSuccess || d_osc2[b].ensure(nc * k * 4) != hipSuccess))
-        rc = fail(ALS_E_OUT_OF_MEMORY, "top-k output buffers");
-      // each finished range of the pass goes down on the copy stream
-      const TopkReady copy_out = [&, b, q0](int64_t o0, int64_t o1) -> int {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(ALS_E_HIP, "top-k copy event");
-        ev_rng.push_back(e);
-        if (hipEventRecord(e, c->st) != hipSuccess || hipStreamWaitEvent(cs, e, 0) != hipSuccess ||
-            hipMemcpyAsync(dst_ids_out + (q0 + o0) * k, d_oid2[b].as<int32_t>() + o0 * k, (o1 - o0) * k * 4,
-                           hipMemcpyDeviceToHost, cs) != hipSuccess ||
-            hipMemcpyAsync(scores_out + (q0 + o0) * k, d_osc2[b].as<float>() + o0 * k, (o1 - o0) * k * 4,
-                           hipMemcpyDeviceToHost, cs) != hipSuccess)
-          return fail(ALS_E_HIP, "top-k result copy");
-        return ALS_OK;
-      };
-      if (rc == ALS_OK)
-        rc = topk_run_rows(c, P, rowsf(q0), q0, q0, nc, d_oid2[b].as<int32_t>(), d_osc2[b].as<float>(), range, copy_out);
-      if (rc == ALS_OK && hipEventRecord(ev_copy[b], cs) != hipSuccess) rc = fail(ALS_E_HIP, "top-k result copy");
-      if (rc != ALS_OK) {
-        end_async();
-        return rc;
-      }
-      stamp("pass");
-      continue;
-    }
-    HIPCHK(d_oid.ensure(nc * k * 4));
-    HIPCHK(d_osc.ensure(nc * k * 4));
-    TRYC(topk_run_rows(c, P, rowsf(q0), q0, q0, nc, d_oid.as<int32_t>(), d_osc.as<float>()));
-    if (dense_out) {
-      HIPCHK(hipMemcpyAsync(dst_ids_out + q0 * k, d_oid.p, nc * k * 4, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(hipMemcpyAsync(scores_out + q0 * k, d_osc.p, nc * k * 4, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(hipStreamSynchronize(c->st));
-    } else {
-      std::vector<int32_t> oid(nc * k);
-      std::vector<float> osc(nc * k);
-      HIPCHK(hipMemcpyAsync(oid.data(), d_oid.p, oid.size() * 4, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(hipMemcpyAsync(osc.data(), d_osc.p, osc.size() * 4, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(hipStreamSynchronize(c->st));
-      for (int64_t i = 0; i < nc; ++i) {
-        std::memcpy(dst_ids_out + posf(q0 + i) * k, &oid[i * k], k * 4);
-        std::memcpy(scores_out + posf(q0 + i) * k, &osc[i * k], k * 4);
-      }
-    }
-  }
-  {
-    const int rc = topk_finish(c, P, sp);
-    if (rc != ALS_OK) {
-      end_async();
-      return rc;
-    }
-  }
-  end_async();
-  stamp("last copies + unpin");
-  if (c->world > 1 && per_rank > 0) {  // every rank ends with every list: one all-gather of the slices
-    std::vector<float> blk((size_t)c->world * per_rank * k * 2, 0.f);
-    float* mine = blk.data() + (size_t)c->rank * per_rank * k * 2;
-    for (int64_t i = lo; i < hi; ++i) {
-      std::memcpy(mine + (size_t)(i - lo) * k * 2, dst_ids_out + posf(i) * k, k * 4);
-      std::memcpy(mine + (size_t)(i - lo) * k * 2 + k, scores_out + posf(i) * k, k * 4);
-    }
-    TRYC(allgather_host(c, blk.data(), per_rank * k * 2));
-    for (int r = 0; r < c->world; ++r) {
-      if (r == c->rank) continue;
-      const int64_t rl = std::min<int64_t>(n_known, (int64_t)r * per_rank), rh = std::min<int64_t>(n_known, rl + per_rank);
-      const float* bb = blk.data() + (size_t)r * per_rank * k * 2;
-      for (int64_t i = rl; i < rh; ++i) {
-        std::memcpy(dst_ids_out + posf(i) * k, bb + (size_t)(i - rl) * k * 2, k * 4);
-        std::memcpy(scores_out + posf(i) * k, bb + (size_t)(i - rl) * k * 2 + k, k * 4);
-      }
-    }
-  }
-  return ALS_OK;
-}
-
-int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, const int32_t* item, const int64_t* key,
-                      double* ndcg_out, int64_t* n_users_out, int32_t* users_out, double* per_user_out, int64_t cap) {
-  if (!c || !ndcg_out || !n_users_out || (n > 0 && (!user || !item || !key)))
-    return fail(ALS_E_INVALID_ARGUMENT, "bad args");
-  if (k <= 0) return fail(ALS_E_INVALID_ARGUMENT, "ranking position k should be positive");
-  if (k > TOPK_KC) return fail(ALS_E_UNSUPPORTED, "NDCG@k on the device supports k <= " + std::to_string(TOPK_KC));
-  TRYC(set_device(c));
-  TRYC(materialize(c, ALS_USER));
-  Side& S = c->s[ALS_USER];
-  *ndcg_out = NAN;
-  *n_users_out = 0;
-  c->last_rescan.clear();
-  c->last_rescan_ready = true;
-  if (n <= 0 || S.n == 0) return ALS_OK;
-  hipStream_t st = c->st;
-  // 1. intoUserActualItems on the device: group by model user (inner join), top-k by (key desc, item asc)
-  DevBuf d_user, d_item, d_key, d_ids, d_row, d_rows, d_idx, d_idxs, d_runs, d_cnt, d_off, d_nr, d_tmp;
-  HIPCHK(d_user.ensure(n * 4));
-  HIPCHK(d_item.ensure(n * 4));
-  HIPCHK(d_key.ensure(n * 8));
-  HIPCHK(d_ids.ensure(S.n * 4));
-  HIPCHK(hipMemcpyAsync(d_user.p, user, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_item.p, item, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_key.p, key, n * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_ids.p, S.ids.data(), S.n * 4, hipMemcpyHostToDevice, st));
-  for (DevBuf* b : {&d_row, &d_rows, &d_idx, &d_idxs, &d_runs, &d_cnt}) HIPCHK(b->ensure(n * 4));
-  HIPCHK(d_off.ensure(n * 8));
-  HIPCHK(d_nr.ensure(8));
-  const size_t tb = eval_sort_temp_bytes(n);
-  HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
-  HIPCHK(eval_group_users(d_user.as<int32_t>(), n, d_ids.as<int32_t>(), S.n, d_tmp.p, tb, d_row.as<uint32_t>(),
-                          d_rows.as<uint32_t>(), d_idx.as<uint32_t>(), d_idxs.as<uint32_t>(), d_runs.as<uint32_t>(),
-                          d_cnt.as<int32_t>(), d_off.as<int64_t>(), d_nr.as<int64_t>(), st));
-  int64_t nr = 0;
-  HIPCHK(hipMemcpyAsync(&nr, d_nr.p, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<int32_t> rows(nr);
-  HIPCHK(hipMemcpyAsync(rows.data(), d_runs.p, nr * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (nr > 0 && (uint32_t)rows[nr - 1] == 0xFFFFFFFFu) --nr;  // ids unknown to the model: dropped
-  rows.resize(nr);
-  *n_users_out = nr;
-  if (nr == 0) return ALS_OK;
-  DevBuf d_act, d_actn, d_gain, d_vals;
-  HIPCHK(d_act.ensure(nr * k * 4));
-  HIPCHK(d_actn.ensure(nr * 4));
-  HIPCHK(eval_actual_lists(d_idxs.as<uint32_t>(), d_off.as<int64_t>(), d_cnt.as<int32_t>(), nr, d_key.as<int64_t>(),
-                           d_item.as<int32_t>(), k, d_act.as<int32_t>(), d_actn.as<int32_t>(), st));
-  // ndcgAt's gains from the host's libm: the host evaluator's table (1.0 / math.log(i + 2))
-  std::vector<double> gain(k);
-  for (int i = 0; i < k; ++i) gain[i] = 1.0 / std::log((double)(i + 2));
-  HIPCHK(d_gain.ensure(k * 8));
-  HIPCHK(hipMemcpyAsync(d_gain.p, gain.data(), k * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(d_vals.ensure(nr * 8));
-  // 2. intoUserPredictedItems: the users' top-k lists stay on the device; 3. ndcgAt per user
-  TopkPlan P;
-  TRYC(topk_plan(c, ALS_USER, k, P));
-  const int64_t per_rank = (nr + c->world - 1) / c->world;
-  const int64_t lo = std::min<int64_t>(nr, (int64_t)c->rank * per_rank), hi = std::min<int64_t>(nr, lo + per_rank);
-  // one pass for any realistic user count (see als_recommend); ALBEDO_TOPK_PASS (test knob): rows per pass
-  const int64_t chunk = [&] {
-    const char* e = std::getenv("ALBEDO_TOPK_PASS");
-    if (e && *e) return std::max<int64_t>(1 << 16, std::atoll(e));
-    return topk_pass_rows(c);
-  }();
-  DevBuf d_oid, d_osc;
-  TRYC(topk_begin(c, P, nr, (hi - lo + chunk - 1) / chunk, rows.data()));
-  for (int64_t q0 = lo; q0 < hi; q0 += chunk) {
-    const int64_t nc = std::min<int64_t>(chunk, hi - q0);
-    HIPCHK(d_oid.ensure(nc * k * 4));
-    HIPCHK(d_osc.ensure(nc * k * 4));
-    TRYC(topk_run_rows(c, P, rows.data() + q0, 0, q0, nc, d_oid.as<int32_t>(), d_osc.as<float>()));
-    HIPCHK(eval_ndcg(d_oid.as<int32_t>(), d_act.as<int32_t>() + q0 * k, d_actn.as<int32_t>() + q0, nc, k,
-                     c->s[ALS_ITEM].n, d_gain.as<double>(), d_vals.as<double>() + q0, st));
-  }
-  TRYC(topk_finish(c, P));
-  std::vector<double> vals((size_t)std::max<int64_t>(per_rank, 1) * c->world, 0.0);
-  if (hi > lo)
-    HIPCHK(hipMemcpyAsync(vals.data() + (size_t)c->rank * per_rank, d_vals.as<double>() + lo, (hi - lo) * 8,
-                          hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->world > 1) TRYC(allgather_host(c, reinterpret_cast<float*>(vals.data()), per_rank * 2));
-  double sum = 0.0;  // mean over users in ascending id order (RankingMetrics: RDD mean)
-  for (int64_t i = 0; i < nr; ++i) sum += vals[i];
-  *ndcg_out = sum / (double)nr;
-  if (nr <= cap) {
-    if (users_out)
-      for (int64_t i = 0; i < nr; ++i) users_out[i] = S.ids[rows[i]];
-    if (per_user_out) std::memcpy(per_user_out, vals.data(), nr * 8);
-  }
-  return ALS_OK;
-}
-
 int als_predict(als_ctx* c, int64_t n, const int32_t* user, const int32_t* item, float* out) {
   if (!c || (n > 0 && (!user || !item || !out))) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
   if (n <= 0) return ALS_OK;
@@ -2474,43 +1541,6 @@ int als_path_stats(const als_ctx* c, int dst_side, int64_t* out4) {
 int als_solver_stats(const als_ctx* c, int dst_side, int64_t* out4) {
   if (!c || (dst_side != 0 && dst_side != 1) || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
   for (int i = 0; i < 4; ++i) out4[i] = c->s[dst_side].solver[i];
-  return ALS_OK;
-}
-
-int als_topk_stats(const als_ctx* c, int64_t* out4) {
-  if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
-  for (int i = 0; i < 4; ++i) out4[i] = c->topk_stats[i];
-  return ALS_OK;
-}
-
-int als_topk_timing(const als_ctx* c, double* out5) {
-  if (!c || !out5) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
-  for (int i = 0; i < 5; ++i) out5[i] = c->topk_ms[i];
-  return ALS_OK;
-}
-
-int als_topk_last_rescan(const als_ctx* c, int32_t* src_ids_out, int64_t cap, int64_t* n_out) {
-  if (!c || !n_out) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
-  if (!c->last_rescan_ready) {  // first query after a top-k call: read its device flags
-    TRYC(set_device(const_cast<als_ctx*>(c)));
-    std::vector<int32_t> need((size_t)c->last_need_n);
-    if (c->last_need_n > 0) {
-      HIPCHK(hipStreamSynchronize(c->st));
-      HIPCHK(copy_st(c, need.data(), c->d_last_need.p, need.size() * 4, hipMemcpyDeviceToHost));
-    }
-    const Side& S = c->s[c->last_src];
-    c->last_rescan.clear();
-    const int64_t nrow = (int64_t)S.ids.size();
-    for (int64_t p = 0; p < c->last_need_n; ++p) {
-      if (!need[p]) continue;
-      const int64_t r = c->last_rows_dense ? p : (p < (int64_t)c->last_rows.size() ? c->last_rows[p] : -1);
-      if (r < 0 || r >= nrow) return fail(ALS_E_STATE, "top-k rescan flags out of range of the src rows");
-      c->last_rescan.push_back(S.ids[r]);
-    }
-    c->last_rescan_ready = true;
-  }
-  *n_out = (int64_t)c->last_rescan.size();
-  if (src_ids_out && *n_out <= cap) std::memcpy(src_ids_out, c->last_rescan.data(), c->last_rescan.size() * 4);
   return ALS_OK;
 }
 

@@ -1,0 +1,221 @@
+// What the host translation units share (als_engine.cpp: contexts, ingest, sweeps; topk_host.cpp:
+// top-k and NDCG): error reporting, the device buffer, the per-side state, the context and the few
+// engine functions the top-k host code calls.  Not part of the public C ABI (include/albedo_als.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "albedo_als.h"
+
+namespace albedo {
+
+// records the message als_last_error returns on this thread (one thread_local, in als_engine.cpp)
+int fail(int code, const std::string& msg);
+
+#define HIPCHK(x)                                                                                  \
+  do {                                                                                             \
+    hipError_t e_ = (x);                                                                           \
+    if (e_ != hipSuccess)                                                                          \
+      return fail(e_ == hipErrorOutOfMemory ? ALS_E_OUT_OF_MEMORY : ALS_E_HIP,                     \
+                  std::string("HIP error: ") + hipGetErrorString(e_) + " in " #x);                 \
+  } while (0)
+#define TRYC(x)                    \
+  do {                             \
+    int rc_ = (x);                 \
+    if (rc_ != ALS_OK) return rc_; \
+  } while (0)
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  bool owned = true;  // false: a view of another context's buffer (als_fork), never freed here
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p && owned) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    owned = true;
+  }
+  void share(const DevBuf& o) {
+    release();
+    p = o.p;
+    bytes = o.bytes;
+    owned = false;
+  }
+  hipError_t ensure(size_t b) {
+    if (!owned) return hipErrorNotSupported;  // a view (als_fork) is never resized or written through
+    if (b <= bytes && p) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&p, b ? b : 16);
+    if (e == hipSuccess) bytes = b;
+    return e;
+  }
+  template <class T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// An owned non-blocking stream / event (null until created); destroyed without waiting, so whoever
+// holds one synchronises before it goes
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { reset(); }
+  bool create() {
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
+    return s != nullptr;
+  }
+  void reset() {
+    if (s) (void)hipStreamDestroy(s);
+    s = nullptr;
+  }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { reset(); }
+  bool create() {
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
+    return e != nullptr;
+  }
+  void reset() {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+};
+
+enum { B_L16 = 0, B_L32 = 1, B_L64 = 2, B_L96 = 3, B_HEAVY = 4, NBUCKET = 5 };
+
+struct Side {
+  int64_t n = 0;                 // rows (unique raw ids)
+  std::vector<int32_t> ids;      // ascending
+  std::vector<int64_t> starts;   // shard starts over dense rows (world + 1)
+  int64_t maxrows = 0;           // max own rows over ranks
+  // Gathered (padded) layout, chunk-major so that one chunk of every rank is contiguous: rank r's
+  // local row i sits at (i / chpad)·world·chpad + r·chpad + i % chpad.  world = 1: nch = 1 and
+  // the position is i.  prows() = nch·world·chpad rows.
+  int nch = 1, world = 1;
+  int64_t chpad = 0;
+  int64_t own0 = 0, own_n = 0;   // this rank's dense row range
+  // dst CSR of this side restricted to own rows (local row index; col = padded src position)
+  DevBuf d_ptr, d_col, d_val;
+  int64_t own_nnz = 0;
+  std::vector<int64_t> h_deg;    // degree per own row
+  DevBuf d_rows;                 // own local rows grouped by bucket
+  DevBuf d_desc;                 // int4 per d_rows entry: {row, p0 lo, p0 hi, degree} (light16 prefetch)
+  int64_t boff[NBUCKET + 1] = {0};
+  int64_t bnnz[NBUCKET] = {0};
+  float vmax = 0.f;              // max |rating| over own dst rows (heavy-build fp16 scaling)
+  float vmin = 0.f;              // min |rating| over own dst rows: vmin == vmax -> one confidence c
+  DevBuf d_X;                    // [own_n][KP] factors in basis B
+  DevBuf d_Z;                    // [prows][KP] rotated factors (src role), gathered layout
+  DevBuf d_Xfull;                // world > 1: [prows][KP] every rank's X (basis B), gathered layout
+  bool full_valid = false;       // d_Xfull holds the current X (gathered behind the solve on st2)
+  int64_t prows() const { return (int64_t)nch * world * chpad; }
+  int64_t pos(int r, int64_t i) const { return (i / chpad) * world * chpad + (int64_t)r * chpad + i % chpad; }
+  DevBuf d_B;                    // fp64 [KP][KP] orthogonal basis on the device: original = X · Bᵀ
+  DevBuf d_Gk;                   // fp64 [KP][KP] last Gram of this side (as src), in basis d_GB
+  DevBuf d_GB;                   // fp64 [KP][KP] the side's basis when d_Gk was computed (G_orig = GB G GBᵀ)
+  bool has_gram = false;
+  bool has_factors = false;
+  double t[ALS_T_COUNT] = {0};
+  int64_t stats[4] = {0};
+  int64_t solver[4] = {0};       // NNLS iterations: sum over rows, max, rows (last half-sweep)
+  DevBuf d_orig;                 // [n][KP] original-basis factors, dense order (materialised)
+  bool orig_valid = false;
+  // split-K of the heavy tail: the first n_split heavy rows (degree > split chunk), their chunks
+  int64_t n_split = 0, n_chunks = 0;
+  DevBuf d_chunk_row, d_chunk_idx, d_slot0;
+  // nonnegative: the first n_batch rows of the (degree-ascending) light list go to the lockstep
+  // NNLS kernel, rows [bat_off[v], bat_off[v+1]) with BATCH_SLOTS[v] slots per workgroup
+  int64_t n_batch = 0, n_batch_nnz = 0;
+  int64_t bat_off[6] = {0};
+  // solve chunks (world > 1, Cholesky path): chunk q's rows of bucket b are the list positions
+  // [cb[b][q], cb[b][q + 1]); its split-K rows are the first split_n[q] of its heavy segment, their
+  // chunk lists start at ck_off[q] and their (chunk-local) slot0 at sl_off[q]
+  int nsolve = 1;
+  int64_t cb[NBUCKET][9] = {{0}};
+  int64_t c8[8] = {0};           // bucket B_L16, solve chunk q: its first c8[q] rows have degree <= 8 (paired)
+  int64_t split_n[8] = {0}, ck_off[9] = {0}, sl_off[8] = {0};
+};
+
+}  // namespace albedo
+
+struct als_ctx {
+  using DevBuf = albedo::DevBuf;
+  using Side = albedo::Side;
+  als_params p{};
+  int KP = 0;
+  int dev = 0;
+  hipStream_t st = nullptr;
+  int rank = 0, world = 1;
+  ncclComm_t comm = nullptr;
+  // host transport (tests: several processes sharing one GPU exchange through the host)
+  int (*h_allreduce)(void*, double*, int64_t) = nullptr;
+  int (*h_allgather)(void*, float*, int64_t) = nullptr;
+  void* h_user = nullptr;
+  Side s[2];
+  int64_t nnz = 0;
+  bool has_ratings = false;
+  bool model_only = false;
+  DevBuf slab, d_G, d_P, d_lam, d_err, d_Gt, d_cs, d_csmax;
+  DevBuf d_eig;                  // device eigensolver scratch (eig.hip)
+  DevBuf d_partial, d_reduced;   // split-K partial / reduced A' records (shared by both sides)
+  DevBuf d_Zhl;                  // pre-split src rows of the uniform-confidence heavy build
+  DevBuf d_Pf;                   // P's bf16 parts in MFMA fragment order (rotate_bf)
+  DevBuf d_iters;                // NNLS iteration counters (sum, max)
+  DevBuf d_gfrag, d_counter;     // lockstep NNLS: G in MFMA operand order, row counter
+  int n_cu = 256;
+  // top-k counters, cumulative: [0] rows through the MFMA scan, [1] rows re-scored by the exact scan
+  // (certification misses), [2] dst chunks scanned, [3] dst chunks a full scan would take
+  int64_t topk_stats[4] = {0, 0, 0, 0};
+  // top-k device time, cumulative (ms, HIP events on st): [0] order + mask, [1] MFMA scan, [2] select,
+  // [3] exact rescans; [4] scan flops (2·KP per src x dst pair the scan's waves scored)
+  double topk_ms[5] = {0, 0, 0, 0, 0};
+  hipEvent_t evt[5] = {};
+  // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
+  // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was
+  // rescanned when d_last_need[p] != 0; its src row is p (last_rows_dense) or last_rows[p]
+  mutable std::vector<int32_t> last_rescan;
+  DevBuf d_last_need;
+  double* h_plan = nullptr;      // pinned: the top-k plan's dst Gram [KP][KP] + two max row norms
+  int64_t last_need_n = 0;
+  std::vector<int32_t> last_rows;
+  mutable bool last_rescan_ready = true;
+  bool last_rows_dense = false;
+  int last_src = 0;
+  int split_len = 0;             // ratings per split-K chunk (0: no split)
+  int slab_blocks = 0;
+  hipEvent_t ev[8] = {};
+  hipStream_t st2 = nullptr;     // world > 1: factor-chunk gathers behind the solve
+  // als_fork: a fork views its parent's ingest buffers; the parent is freed after its last fork
+  als_ctx* parent = nullptr;
+  int forks = 0;
+  bool doomed = false;
+  hipEvent_t evc[9] = {};        // per solve chunk: done on st; [8]: gathers done on st2
+};
+
+namespace albedo {
+
+int set_device(als_ctx* c);
+// Copies between the host and the context's buffers go through the engine stream c->st and complete
+// before returning (als_engine.cpp)
+hipError_t copy_st(const als_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+float event_ms(hipEvent_t a, hipEvent_t b);
+// original-basis factors of `side`, dense order, on device: d_orig [n][KP]
+int materialize(als_ctx* c, int side);
+int64_t find_row(const Side& S, int32_t id);  // dense row of a raw id, -1 when unknown
+// all-gather of host blocks: buf holds world blocks of n floats (this rank's filled)
+int allgather_host(als_ctx* c, float* buf, int64_t n);
+
+}  // namespace albedo
