@@ -25,6 +25,8 @@ ALS_E_OUT_OF_MEMORY = 6
 ALS_E_NO_DEVICE = 7
 ALS_E_UNSUPPORTED = 8
 ALS_USER, ALS_ITEM = 0, 1
+ALS_METRIC_NDCG, ALS_METRIC_PRECISION, ALS_METRIC_MAP = 0, 1, 2
+METRICS = {"NDCG@k": ALS_METRIC_NDCG, "Precision@k": ALS_METRIC_PRECISION, "MAP": ALS_METRIC_MAP}
 ALS_T_COUNT = 8
 T_NAMES = ["gram", "eig", "rotate", "comm", "solve_light", "solve_heavy", "half_total", "_"]
 
@@ -101,6 +103,13 @@ SIGNATURES = [
     ("als_recommend", C.c_int, [P, C.c_int, C.c_int32, I32P, C.c_int64, I32P, I32P, F32P]),
     ("als_predict", C.c_int, [P, C.c_int64, I32P, I32P, F32P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
+    ("als_evaluate_ranking", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P,
+                                       C.c_int64]),
+    ("als_rank_pairs", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, I32P, I32P, I32P, F32P,
+                                 C.c_int64]),
+    ("als_evaluate_pairs", C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, C.c_int64, I32P, I32P,
+                                     I64P, F64P, I64P, I32P, F64P, C.c_int64]),
+    ("als_eval_pairs_timing", C.c_int, [P, F64P]),
     ("als_last_timings", C.c_int, [P, C.c_int, F64P, C.c_int]),
     ("als_path_stats", C.c_int, [P, C.c_int, I64P]),
     ("als_solver_stats", C.c_int, [P, C.c_int, I64P]),

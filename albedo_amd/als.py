@@ -435,6 +435,97 @@ class ALSModel(_Params):
             return mean.value, uo[:nu.value], vo[:nu.value]
         return mean.value
 
+    @staticmethod
+    def _keys_i64(keys):
+        ky = np.asarray(keys)
+        if ky.dtype.kind == "M":  # starred_at timestamps
+            ky = ky.astype("datetime64[us]").astype(np.int64)
+        return np.ascontiguousarray(ky, dtype=np.int64)
+
+    @staticmethod
+    def _metric_code(metric):
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unsupported metric {metric}; supports {', '.join(_lib.METRICS)}")
+        return _lib.METRICS[metric]
+
+    def evaluate_ranking(self, users, items, keys, k=30, metric="NDCG@k", per_user=False):
+        """`evaluate_ndcg` with RankingEvaluator's metricName ("NDCG@k", "Precision@k", "MAP";
+        RankingEvaluator.scala:21,97-101) on the device (als_evaluate_ranking)."""
+        code = self._metric_code(metric)
+        u = np.ascontiguousarray(_checked_cast(users, self._p["userCol"]))
+        it = np.ascontiguousarray(_checked_cast(items, self._p["itemCol"]))
+        ky = self._keys_i64(keys)
+        if not (u.size == it.size == ky.size):
+            raise ValueError("users, items and keys must have the same length")
+        mean = C.c_double()
+        nu = C.c_int64()
+        cap = int(np.unique(u).size) if per_user else 0
+        uo = np.empty(max(cap, 1), np.int32)
+        vo = np.empty(max(cap, 1), np.float64)
+        check(load().als_evaluate_ranking(self._h, code, int(k), u.size, ptr(u, C.c_int32), ptr(it, C.c_int32),
+                                          ptr(ky, C.c_int64), C.byref(mean), C.byref(nu),
+                                          ptr(uo, C.c_int32) if per_user else None,
+                                          ptr(vo, C.c_double) if per_user else None, cap))
+        if per_user:
+            return mean.value, uo[:nu.value], vo[:nu.value]
+        return mean.value
+
+    # ---- held-out pairs (ALSRecommenderCV.scala:54-90, RankingMetricFormatter.scala:59-64) -----------
+    def rank_pairs(self, users, items, topK=15, width=None):
+        """RankingMetricFormatter("als") of transform(pairs) with coldStartStrategy "drop", on the
+        device (als_rank_pairs): per user with a surviving pair, the pairs with rank() over
+        (prediction desc) <= topK in (score desc, item asc) order, cut to `width` (default topK; ties
+        at the boundary make a list longer than topK).  Returns (user ids ascending, lengths,
+        items [n, width] padded with -1, scores [n, width] padded with NaN)."""
+        width = int(topK if width is None else width)
+        u = np.ascontiguousarray(_checked_cast(users, self._p["userCol"]))
+        it = np.ascontiguousarray(_checked_cast(items, self._p["itemCol"]))
+        if u.size != it.size:
+            raise ValueError("users and items must have the same length")
+        cap = max(int(np.unique(u).size), 1)
+        nu = C.c_int64()
+        uo, ln = np.empty(cap, np.int32), np.empty(cap, np.int32)
+        io = np.empty((cap, max(width, 1)), np.int32)
+        so = np.empty((cap, max(width, 1)), np.float32)
+        check(load().als_rank_pairs(self._h, int(topK), width, u.size, ptr(u, C.c_int32), ptr(it, C.c_int32),
+                                    C.byref(nu), ptr(uo, C.c_int32), ptr(ln, C.c_int32), ptr(io, C.c_int32),
+                                    ptr(so, C.c_float), cap))
+        n = nu.value
+        return uo[:n], ln[:n], io[:n], so[:n]
+
+    def evaluate_pairs(self, users, items, actual_users, actual_items, actual_keys, metric="NDCG@k", topK=15, k=30,
+                       per_user=False):
+        """RankingEvaluator(metric, k).evaluate of `rank_pairs(users, items, topK, width=k)` against
+        intoUserActualItems(actual_*, keys desc, k), without the lists leaving the device
+        (als_evaluate_pairs): one fold's step of ALSRecommenderCV.scala:72-90.  Returns the mean, or
+        (mean, user ids, per-user values) with per_user=True."""
+        code = self._metric_code(metric)
+        u = np.ascontiguousarray(_checked_cast(users, self._p["userCol"]))
+        it = np.ascontiguousarray(_checked_cast(items, self._p["itemCol"]))
+        au = np.ascontiguousarray(_checked_cast(actual_users, self._p["userCol"]))
+        ai = np.ascontiguousarray(_checked_cast(actual_items, self._p["itemCol"]))
+        ak = self._keys_i64(actual_keys)
+        if u.size != it.size or not (au.size == ai.size == ak.size):
+            raise ValueError("the columns of the pairs, and those of the actual rows, must have the same length")
+        mean = C.c_double()
+        nu = C.c_int64()
+        cap = int(np.unique(u).size) if per_user else 0
+        uo = np.empty(max(cap, 1), np.int32)
+        vo = np.empty(max(cap, 1), np.float64)
+        check(load().als_evaluate_pairs(self._h, code, int(topK), int(k), u.size, ptr(u, C.c_int32), ptr(it, C.c_int32),
+                                        au.size, ptr(au, C.c_int32), ptr(ai, C.c_int32), ptr(ak, C.c_int64),
+                                        C.byref(mean), C.byref(nu), ptr(uo, C.c_int32) if per_user else None,
+                                        ptr(vo, C.c_double) if per_user else None, cap))
+        if per_user:
+            return mean.value, uo[:nu.value], vo[:nu.value]
+        return mean.value
+
+    def eval_pairs_timing(self):
+        """Device ms of the last rank_pairs / evaluate_pairs: map, sort, score, select, metric."""
+        out = np.zeros(5, np.float64)
+        check(load().als_eval_pairs_timing(self._h, ptr(out, C.c_double)))
+        return dict(zip(("map", "sort", "score", "select", "metric"), out.tolist()))
+
     # ---- persistence (Spark 2.2 ALSModelWriter / ALSModelReader layout: albedo_amd/persistence.py) ----
     MODEL_PARAMS = ("userCol", "itemCol", "predictionCol", "coldStartStrategy")  # ALSModelParams
 

@@ -1,5 +1,5 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, sweeps; topk_host.cpp:
-// top-k and NDCG): error reporting, the device buffer, the per-side state, the context and the few
+// top-k and NDCG; eval_host.cpp: held-out pair ranking): error reporting, the device buffer, the per-side state, the context and the few
 // engine functions the top-k host code calls.  Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -182,6 +182,8 @@ struct als_ctx {
   // top-k device time, cumulative (ms, HIP events on st): [0] order + mask, [1] MFMA scan, [2] select,
   // [3] exact rescans; [4] scan flops (2·KP per src x dst pair the scan's waves scored)
   double topk_ms[5] = {0, 0, 0, 0, 0};
+  // device time of the last pair-ranking call (ms): map, sort, score, select, metric (als_eval_pairs_timing)
+  double eval_ms[5] = {0, 0, 0, 0, 0};
   hipEvent_t evt[5] = {};
   // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
   // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was

@@ -246,6 +246,37 @@ hipError_t eval_actual_lists(const uint32_t* idx_sorted, const int64_t* offsets,
 // the rest padding) against act; gain[i] = 1 / ln(i + 2)
 hipError_t eval_ndcg(const int32_t* pred, const int32_t* act, const int32_t* act_n, int64_t n_users, int k,
                      int64_t n_dst, const double* gain, double* out, hipStream_t s);
+// ---- held-out pair ranking (eval_pairs.hip): RankingMetricFormatter("als") of transform(pairs) ------
+constexpr int PAIRS_SEG = 4096;  // entries one wave selects from; a longer user is cut into segments
+size_t pairs_sort_temp_bytes(int64_t n, int64_t n_users);
+// raw ids -> rows of the ascending tables; urow = n_u and irow = 0 when either id is unknown
+hipError_t pairs_map(const int32_t* user, const int32_t* item, int64_t n, const int32_t* uids, int64_t n_u,
+                     const int32_t* iids, int64_t n_i, uint32_t* urow, uint32_t* irow, hipStream_t s);
+// (urow, irow) sorted by urow (stable), then runs[r] (user row) with counts[r] pairs from offsets[r]; the
+// dropped pairs' run (row n_u) is the last one when present; *n_runs_host is valid on return
+hipError_t pairs_group(int64_t n, int64_t n_u, void* temp, size_t temp_bytes, const uint32_t* urow,
+                       uint32_t* urow_sorted, const uint32_t* irow, uint32_t* irow_sorted, uint32_t* runs,
+                       int32_t* counts, int64_t* offsets, int64_t* n_runs, int64_t* n_runs_host, hipStream_t s);
+// ent[p] = {bits of F2J sdot(U[urow_sorted[p]], V[irow_sorted[p]]), iids[irow_sorted[p]]} for p < n_live
+hipError_t pairs_score(int KP, int kreal, const float* U, const float* V, const uint32_t* urow_sorted,
+                       const uint32_t* irow_sorted, const int32_t* iids, int64_t n_live, uint2* ent, hipStream_t s);
+// per run of at most PAIRS_SEG entries: the entries with rank() <= top_k in (score desc, item asc) order, cut
+// to width -> items / scores [n_runs][width] (-1 / NaN padded), len; NaN scores are dropped; longer runs
+// are left to pairs_select_long
+hipError_t pairs_select(const uint2* ent, const int64_t* offsets, const int32_t* counts, int64_t n_runs, int top_k,
+                        int width, int32_t* items, float* scores, int32_t* len, hipStream_t s);
+// the runs longer than PAIRS_SEG: segment g (seg_cnt[g] <= PAIRS_SEG entries from seg_off[g]) leaves its best
+// 64 keys in seg_keys[g][64]; long run j merges key_cnt[j] keys from seg_keys + key_off[j] into row run[j]
+hipError_t pairs_select_long(const uint2* ent, const int64_t* seg_off, const int32_t* seg_cnt, int64_t n_seg,
+                             uint64_t* seg_keys, const int64_t* key_off, const int32_t* key_cnt, const int32_t* run,
+                             int64_t n_long, int top_k, int width, int32_t* items, float* scores, int32_t* len,
+                             hipStream_t s);
+// metric (ALS_METRIC_*) of evaluated user u: predicted list pred[pred_row[u]] ([.][pred_width], its first
+// pred_len[.] entries; pred_len null: np_all for every user; pred_row null: u) against actual list
+// act[act_row[u]] ([.][k] with act_n; act_row null: u); every list is cut to k
+hipError_t eval_metric(int metric, const int32_t* pred, int pred_width, const int32_t* pred_len, int np_all,
+                       const int32_t* pred_row, const int32_t* act, const int32_t* act_n, const int32_t* act_row,
+                       int64_t n_users, int k, const double* gain, double* out, hipStream_t s);
 // *out = bits of max_r ||T[r][0..kreal)||_2 computed in fp64
 hipError_t launch_rownorm_max(const float* T, int64_t n, int KP, int kreal, unsigned long long* out, hipStream_t s);
 

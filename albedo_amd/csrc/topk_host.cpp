@@ -1,6 +1,6 @@
 // Host side of top-k (topk.hip) and NDCG (eval.hip): the per-call plan of the dst side, the passes over
 // the src rows, the three ways a call's lists reach the caller's arrays, and the C ABI entry points
-// als_recommend, als_evaluate_ndcg and the top-k counters.
+// als_recommend, als_evaluate_ndcg, als_evaluate_ranking and the top-k counters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -805,8 +805,11 @@ int als_recommend(als_ctx* c, int side, int32_t k, const int32_t* subset, int64_
   return ALS_OK;
 }
 
-int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, const int32_t* item, const int64_t* key,
-                      double* ndcg_out, int64_t* n_users_out, int32_t* users_out, double* per_user_out, int64_t cap) {
+// RankingEvaluator.evaluate of the users' own top-k lists: als_evaluate_ndcg (metric = ALS_METRIC_NDCG, through
+// eval_ndcg) and als_evaluate_ranking (Precision@k and MAP through eval_metric)
+static int evaluate_topk_lists(als_ctx* c, int32_t metric, int32_t k, int64_t n, const int32_t* user, const int32_t* item,
+                               const int64_t* key, double* ndcg_out, int64_t* n_users_out, int32_t* users_out,
+                               double* per_user_out, int64_t cap) {
   if (!c || !ndcg_out || !n_users_out || (n > 0 && (!user || !item || !key)))
     return fail(ALS_E_INVALID_ARGUMENT, "bad args");
   if (k <= 0) return fail(ALS_E_INVALID_ARGUMENT, "ranking position k should be positive");
@@ -875,8 +878,13 @@ int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, con
     o.ids = d_oid.as<int32_t>();
     o.scores = d_osc.as<float>();
     TRYC(topk_run_rows(c, P, rows.data() + q0, 0, q0, nc, o));
-    HIPCHK(eval_ndcg(d_oid.as<int32_t>(), d_act.as<int32_t>() + q0 * k, d_actn.as<int32_t>() + q0, nc, k,
-                     c->s[ALS_ITEM].n, d_gain.as<double>(), d_vals.as<double>() + q0, st));
+    if (metric == ALS_METRIC_NDCG)
+      HIPCHK(eval_ndcg(d_oid.as<int32_t>(), d_act.as<int32_t>() + q0 * k, d_actn.as<int32_t>() + q0, nc, k,
+                       c->s[ALS_ITEM].n, d_gain.as<double>(), d_vals.as<double>() + q0, st));
+    else
+      HIPCHK(eval_metric(metric, d_oid.as<int32_t>(), k, nullptr, (int)std::min<int64_t>(k, c->s[ALS_ITEM].n), nullptr,
+                         d_act.as<int32_t>() + q0 * k, d_actn.as<int32_t>() + q0, nullptr, nc, k, d_gain.as<double>(),
+                         d_vals.as<double>() + q0, st));
   }
   TRYC(topk_finish(c, P));
   std::vector<double> vals((size_t)std::max<int64_t>(per_rank, 1) * c->world, 0.0);
@@ -895,6 +903,21 @@ int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, con
   }
   return ALS_OK;
 }
+
+int als_evaluate_ndcg(als_ctx* c, int32_t k, int64_t n, const int32_t* user, const int32_t* item, const int64_t* key,
+                      double* ndcg_out, int64_t* n_users_out, int32_t* users_out, double* per_user_out, int64_t cap) {
+  return evaluate_topk_lists(c, ALS_METRIC_NDCG, k, n, user, item, key, ndcg_out, n_users_out, users_out, per_user_out,
+                             cap);
+}
+
+int als_evaluate_ranking(als_ctx* c, int32_t metric, int32_t k, int64_t n, const int32_t* user, const int32_t* item,
+                         const int64_t* key, double* mean_out, int64_t* n_users_out, int32_t* users_out,
+                         double* per_user_out, int64_t cap) {
+  if (metric != ALS_METRIC_NDCG && metric != ALS_METRIC_PRECISION && metric != ALS_METRIC_MAP)
+    return fail(ALS_E_INVALID_ARGUMENT, "unknown metric " + std::to_string(metric));
+  return evaluate_topk_lists(c, metric, k, n, user, item, key, mean_out, n_users_out, users_out, per_user_out, cap);
+}
+
 int als_topk_stats(const als_ctx* c, int64_t* out4) {
   if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
   for (int i = 0; i < 4; ++i) out4[i] = c->topk_stats[i];

@@ -162,6 +162,45 @@ int als_recommend(als_ctx* ctx, int side, int32_t k, const int32_t* subset, int6
  * and per_user_out are filled when non-null and *n_users_out <= cap.  1 <= k <= 64. */
 int als_evaluate_ndcg(als_ctx* ctx, int32_t k, int64_t n, const int32_t* user, const int32_t* item, const int64_t* key,
                       double* ndcg_out, int64_t* n_users_out, int32_t* users_out, double* per_user_out, int64_t cap);
+/* RankingEvaluator's metrics (RankingEvaluator.scala:21, :97-101 -> mllib RankingMetrics.ndcgAt(k),
+ * precisionAt(k), meanAveragePrecision). */
+enum { ALS_METRIC_NDCG = 0, ALS_METRIC_PRECISION = 1, ALS_METRIC_MAP = 2 };
+/* als_evaluate_ndcg with a metric (RankingEvaluator.scala:97-101): the model's own top-k recommendations as
+ * the predicted lists, the same actual lists, inner join and rank slicing.  ALS_METRIC_NDCG returns exactly
+ * als_evaluate_ndcg's values.  Precision@k = hits in the first min(|pred|, k) / k; MAP = sum over hit
+ * positions i of hits_so_far / (i + 1), divided by |labSet| (distinct actual items); fp64, index order. */
+int als_evaluate_ranking(als_ctx* ctx, int32_t metric, int32_t k, int64_t n, const int32_t* user, const int32_t* item,
+                         const int64_t* key, double* mean_out, int64_t* n_users_out, int32_t* users_out,
+                         double* per_user_out, int64_t cap);
+/* RankingMetricFormatter("als") (RankingMetricFormatter.scala:59-64, RankingEvaluator.scala:131-139) of
+ * ALSModel.transform(pairs) with coldStartStrategy = "drop", the predicted side of the cross-validation
+ * job (ALSRecommenderCV.scala:54-90), on the device: every (user, item) pair whose ids the model knows is
+ * scored with the F2J sdot; pairs with an unknown id or a NaN score are dropped; per user the pairs with
+ * rank() over (score desc) <= top_k stay (ties at the boundary all stay), in (score desc, item asc)
+ * order, cut to `width` entries.  +-inf scores order normally, -0.0 and +0.0 tie, a repeated (user, item)
+ * pair stays once per copy.  One row per user with at least one surviving pair, ascending user ids:
+ * users_out / len_out [cap], items_out / scores_out [cap][width] padded with -1 / NaN; each is filled when
+ * non-null and *n_users_out <= cap.  1 <= top_k, width <= 64.  world > 1: ALS_E_UNSUPPORTED (contexts
+ * from als_model_create are single-process; a sharded fit is evaluated through its model). */
+int als_rank_pairs(als_ctx* ctx, int32_t top_k, int32_t width, int64_t n, const int32_t* user, const int32_t* item,
+                   int64_t* n_users_out, int32_t* users_out, int32_t* len_out, int32_t* items_out, float* scores_out,
+                   int64_t cap);
+/* RankingEvaluator.evaluate (RankingEvaluator.scala:83-103) of those lists with width = k against
+ * intoUserActualItems(act_user, act_item, act_key desc, k) (:111-129), as ALSRecommenderCV.scala:72-90 and
+ * albedo_toolkit/evaluators.py:42-67 do per fold: the users with at least one surviving predicted pair and
+ * at least one actual row (inner join), ascending ids; the mean is their left-to-right sum divided by
+ * their count (NaN when nobody is left).  Per-user values are bit-identical to the host evaluator's on the
+ * same lists; a predicted item repeated in a list counts as a hit each time, as in mllib.  users_out and
+ * per_user_out are filled when non-null and *n_users_out <= cap.  1 <= top_k, k <= 64.  world > 1:
+ * ALS_E_UNSUPPORTED. */
+int als_evaluate_pairs(als_ctx* ctx, int32_t metric, int32_t top_k, int32_t k, int64_t n_pairs, const int32_t* user,
+                       const int32_t* item, int64_t n_act, const int32_t* act_user, const int32_t* act_item,
+                       const int64_t* act_key, double* mean_out, int64_t* n_users_out, int32_t* users_out,
+                       double* per_user_out, int64_t cap);
+/* Device time of the last als_rank_pairs / als_evaluate_pairs call from HIP events on the context's
+ * stream (ms): out[0] = id mapping, out[1] = sort + run lengths, out[2] = scoring, out[3] = list
+ * selection, out[4] = actual lists + metric (als_evaluate_pairs only). */
+int als_eval_pairs_timing(const als_ctx* ctx, double* out5);
 /* ALSModel.transform: F2J sdot per (user, item) pair; NaN when either id is unknown. */
 int als_predict(als_ctx* ctx, int64_t n, const int32_t* user, const int32_t* item, float* out);
 
