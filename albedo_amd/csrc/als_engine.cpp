@@ -104,18 +104,31 @@ int validate(const als_params* p) {
 // Rows of degree <= light_limit take the push-through solve (a d x d system).  d <= 64 by default;
 // light_max_degree up to 96 (KP = 128) routes rows of degree 65..96 through the d x d path too
 // (solve_light_kernel<128, 96>), measured against the explicit k x k wave kernel in DESIGN §4.
+// The limit is also what als_path_stats calls "light"; the degree tiers below do not move it.
 int64_t light_limit(const als_ctx* c) {
   if (c->p.light_max_degree >= 0) return std::min<int64_t>(c->p.light_max_degree, c->KP == 128 ? 96 : 64);
   return c->KP >= 128 ? 64 : 32;
 }
 
-int bucket_of(int64_t d, int64_t lmax) {
+// Degree tiers (KP = 128, the default light limit, Cholesky path): rows of degree 33..48 take
+// solve_light_kernel<128, 48> (3 panels, 6 tiles instead of 4 and 10) and rows of degree 65..80, which
+// are above the light limit, take solve_light_kernel<128, 80> at three waves per SIMD instead of the
+// wave kernel.  An explicit light_max_degree keeps the routing it names.
+// ALBEDO_DEGREE_TIERS=0 switches the tiers off (the A/B handle, read when the row layout is built).
+bool degree_tiers_on(const als_ctx* c) {
+  if (c->KP != 128 || c->p.light_max_degree != -1 || c->p.nonnegative) return false;
+  const char* e = std::getenv("ALBEDO_DEGREE_TIERS");
+  return !(e && *e && std::atoi(e) == 0);
+}
+
+int bucket_of(int64_t d, int64_t lmax, bool tiers) {
   if (d <= lmax) {
     if (d <= 16) return B_L16;
     if (d <= 32) return B_L32;
+    if (tiers && d <= 48) return B_L48;
     return d <= 64 ? B_L64 : B_L96;
   }
-  return B_HEAVY;
+  return (tiers && d <= 80) ? B_M80 : B_HEAVY;
 }
 
 // ---- collectives ------------------------------------------------------------------------------
@@ -233,13 +246,14 @@ int rank_layout(als_ctx* c) {
   TRYC(drain(c));
   const int64_t lmax = light_limit(c);
   c->split_len = split_chunk_len();
+  c->tiers = degree_tiers_on(c);
   for (int side = 0; side < 2; ++side) {
     Side& S = c->s[side];
     // degree buckets (heavy rows longest first for the tail)
     std::vector<int32_t> rows[NBUCKET];
     for (int b = 0; b < NBUCKET; ++b) S.bnnz[b] = 0;
     for (int64_t r = 0; r < S.own_n; ++r) {
-      const int b = bucket_of(S.h_deg[r], lmax);
+      const int b = bucket_of(S.h_deg[r], lmax, c->tiers);
       rows[b].push_back((int32_t)r);
       S.bnnz[b] += S.h_deg[r];
     }
@@ -563,7 +577,8 @@ bool rotate_bf_on(const als_ctx* c) { return c->KP == 128; }
 // already wrote it (rotate_bf)
 bool presplit_wanted(const als_ctx* c, const Side& T, float* sw) {
   const bool uniform = !c->p.implicit_prefs || (T.vmin == T.vmax && T.vmax > 0.f);
-  if (!uniform || !use_wave_kernel(c) || T.boff[NBUCKET] == T.boff[B_HEAVY]) return false;
+  // rows above the light limit: B_M80 counts, since a forced-heavy half sends it to the wave kernel
+  if (!uniform || !use_wave_kernel(c) || T.boff[NBUCKET] == T.boff[B_LIGHT_END]) return false;
   const float cw = c->p.implicit_prefs ? (float)c->p.alpha * T.vmax : 1.0f;
   if (!(cw > 0.f)) return false;
   *sw = std::sqrt(cw);
@@ -890,18 +905,24 @@ int half_sweep(als_ctx* c, int t) {
   a.colscale = c->d_cs.as<float>();
   a.n_cu = c->n_cu;
   const int32_t* rows = T.d_rows.as<int32_t>();
-  static const int Dof[B_HEAVY] = {16, 32, 64, 96};
+  static const int Dof[B_HEAVY] = {16, 32, 48, 64, 96, 80};
+  // als_path_stats: light = the rows within the light limit; the tier bucket B_M80 (degree 65..80) is
+  // above it and counts with the heavy rows, whichever kernel solves it
   T.stats[0] = T.stats[1] = T.stats[2] = T.stats[3] = 0;
-  for (int b = 0; b < B_HEAVY; ++b) {
+  for (int b = 0; b < B_LIGHT_END; ++b) {
     T.stats[force_heavy ? 2 : 0] += T.boff[b + 1] - T.boff[b];
     T.stats[force_heavy ? 3 : 1] += T.bnnz[b];
   }
-  T.stats[2] += T.boff[B_HEAVY + 1] - T.boff[B_HEAVY];
-  T.stats[3] += T.bnnz[B_HEAVY];
+  for (int b = B_LIGHT_END; b < NBUCKET; ++b) {
+    T.stats[2] += T.boff[b + 1] - T.boff[b];
+    T.stats[3] += T.bnnz[b];
+  }
   // Solve chunk by chunk (one chunk unless world > 1); world > 1: each finished chunk of the new
-  // factors is gathered on the second stream while the next chunk solves
+  // factors is gathered on the second stream while the next chunk solves.  B_M80 is
+  // launched behind the light / heavy timer event: its rows and bytes count as heavy.
   for (int q = 0; q < T.nsolve; ++q) {
     for (int b = 0; b < B_HEAVY; ++b) {
+      if (b == B_LIGHT_END && T.nsolve == 1) HIPCHK(hipEventRecord(ev[5], st));
       a.rows = rows + T.cb[b][q];
       a.desc = T.d_desc.as<int32_t>() + 4 * T.cb[b][q];
       a.n_rows = T.cb[b][q + 1] - T.cb[b][q];
@@ -917,7 +938,6 @@ int half_sweep(als_ctx* c, int t) {
         HIPCHK(launch_solve_light16(KP, p16, st, false));
       } else HIPCHK(launch_solve_light(KP, Dof[b], a, st));
     }
-    if (T.nsolve == 1) HIPCHK(hipEventRecord(ev[5], st));
     TRYC(heavy_launches(c, T, a, T.cb[B_HEAVY][q], T.cb[B_HEAVY][q + 1] - T.cb[B_HEAVY][q], false, q));
     if (multi) {
       HIPCHK(hipEventRecord(c->evc[q], st));
@@ -1126,6 +1146,7 @@ int als_fork(als_ctx* parent, const als_params* p, als_ctx** out) {
   // the ingest and the rank layout are the parent's (read-only during a fit): views, not copies
   c->nnz = parent->nnz;
   c->split_len = parent->split_len;
+  c->tiers = parent->tiers;
   for (int side = 0; side < 2; ++side) {
     Side& S = c->s[side];
     const Side& P = parent->s[side];

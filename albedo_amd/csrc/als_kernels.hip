@@ -653,17 +653,21 @@ hipError_t launch_rotate(int KP, const float* X, const float* M, float* Z, int64
 __host__ __device__ constexpr int light_wave_lds(int D) { return D == 16 ? D * (D + 1) / 2 + 64 : wchol_scratch_floats(D / 16); }
 
 // workgroups per CU: D = 32 at KP = 128 keeps its gathered rows in registers (KEEPZ) and spilled 16
-// VGPRs at 4 (128 VGPRs); at 3 (168) it does not, and the user light half is 1.9 ms faster (r04 A/B)
+// VGPRs at 4 (128 VGPRs); at 3 (168) it does not, and the user light half is 1.9 ms faster (r04 A/B).
+// The degree tiers of KP = 128: D = 80 fits 3 (168 VGPRs, no scratch; D = 96 would spill
+// 124-196 B there and stays at 2).  D = 48 runs at 5 (96 VGPRs + 8 B of scratch): 3.62 ms per c4 sweep
+// against 3.69-3.71 at 4 (103 VGPRs, no scratch) in the kernel trace.
 template <int KP, int D>
 constexpr int light_occupancy() {
-  return D > 64 ? 2 : (D == 16 && KP <= 128) ? 6 : (KP == 128 && D == 32) ? 3 : (KP <= 128) ? 4 : 2;
+  return (KP == 128 && D == 80) ? 3 : (KP == 128 && D == 48) ? 5 : D > 64 ? 2 : (D == 16 && KP <= 128) ? 6 :
+         (KP == 128 && D == 32) ? 3 : (KP <= 128) ? 4 : 2;
 }
 
-// the split-fp16 S build (and its column-scale bound) serves D >= 64 and the register-resident rows
+// the split-fp16 S build (and its column-scale bound) serves D >= 48 and the register-resident rows
 template <int KP, int D>
 constexpr bool light_keepz() { return D <= 32 && D * KP <= 4096; }
 template <int KP, int D>
-constexpr bool light_split_s() { return D >= 64 || light_keepz<KP, D>(); }
+constexpr bool light_split_s() { return D >= 48 || light_keepz<KP, D>(); }
 
 // One light row: j, degree d (wave-uniform), lane e < d holds rating r and src row colE of entry e;
 // D > 64: lane e also holds entry 64 + e (r2, colE2).  lamv[h] / icsv[h]: a.lam and the inverse column
@@ -702,7 +706,7 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
 #pragma unroll
       for (int c = 0; c < NC; ++c) zf[I][c] = vB[I] ? ld4(a.Z + (int64_t)colB[I] * KP + 16 * c + 4 * g) : zero4();
   }
-  // D >= 64 re-gathers the rows per 32-column step of the S build, and no gather is conditional: a
+  // D >= 48 re-gathers the rows per 32-column step of the S build, and no gather is conditional: a
   // lane whose entry is past the row end or masked (c = 0) gathers the zero row of Z (a.zero_row, as
   // light16.hip does), which gives exactly the zeros the skipped load used to stand for, so all 2·NB
   // loads of a step are in flight before the first wait.  Step 0 goes out here, ahead of the D^-1/2
@@ -710,9 +714,12 @@ __device__ __forceinline__ void light_row(const SolveArgs& a, int j, int d, floa
   // step q's values are converted, so those loads fly behind step q's MFMAs; the last LATE blocks are
   // loaded at the start of their own step, behind the converts of the others.  KP = 128, D = 64 runs
   // at 4 workgroups per CU (128 VGPRs): LATE = 0 needs 128 + 28 B of scratch, LATE = 2 127 and none,
-  // no look-ahead at all 113 (and measured 1.3 % slower than LATE = 2); the other instances fit LATE = 0.
-  constexpr bool PUSHG = !KEEPZ && D >= 64;
-  constexpr int LATE = (KP == 128 && D == 64) ? 2 : 0;
+  // no look-ahead at all 113 (and measured 1.3 % slower than LATE = 2); D = 80 at 3 workgroups per CU
+  // (168 VGPRs): LATE = 0 / 2 need 52 / 24 B of scratch, LATE = 3 168 VGPRs and none (10.75 ms per c4
+  // sweep), LATE = 4 160 (10.89 ms), LATE = 5, no look-ahead, 158 (11.10 ms); the other instances fit
+  // LATE = 0.
+  constexpr bool PUSHG = !KEEPZ && D >= 48;
+  constexpr int LATE = (KP == 128 && D == 64) ? 2 : (KP == 128 && D == 80) ? 3 : 0;
   f32x4 zr0[PUSHG ? NB : 1], zr1[PUSHG ? NB : 1];
   const float* zpB[PUSHG ? NB : 1];
   if constexpr (PUSHG) {
@@ -1038,7 +1045,7 @@ hipError_t launch_solve_light(int KP, int D, const SolveArgs& a0, hipStream_t s)
 #define LIGHT(kp, dd) \
   if (KP == kp && D == dd) { solve_light_kernel<kp, dd><<<blocks, 256, lds, s>>>(a); return hipGetLastError(); }
   LIGHT(64, 16) LIGHT(64, 32) LIGHT(64, 64) LIGHT(128, 16) LIGHT(128, 32) LIGHT(128, 64)
-  LIGHT(256, 16) LIGHT(256, 32) LIGHT(256, 64) LIGHT(128, 96)
+  LIGHT(256, 16) LIGHT(256, 32) LIGHT(256, 64) LIGHT(128, 96) LIGHT(128, 48) LIGHT(128, 80)
 #undef LIGHT
   return hipErrorInvalidValue;
 }

@@ -94,7 +94,12 @@ struct Event {
   }
 };
 
-enum { B_L16 = 0, B_L32 = 1, B_L64 = 2, B_L96 = 3, B_HEAVY = 4, NBUCKET = 5 };
+// Row buckets in list order.  B_L16 .. B_L96 hold the rows within the light limit (push-through
+// solve); B_L48 (degree 33..48) and B_M80 (degree 65..80, above the default light limit of 64) exist
+// only with the degree tiers on (als_ctx::tiers) and are empty otherwise.  B_M80 rows run the
+// push-through kernel too but count, and are timed, with the rows above the limit (B_LIGHT_END
+// splits the two groups); B_HEAVY rows take the explicit k x k path.
+enum { B_L16 = 0, B_L32 = 1, B_L48 = 2, B_L64 = 3, B_L96 = 4, B_M80 = 5, B_HEAVY = 6, NBUCKET = 7, B_LIGHT_END = B_M80 };
 
 struct Side {
   int64_t n = 0;                 // rows (unique raw ids)
@@ -197,6 +202,7 @@ struct als_ctx {
   bool last_rows_dense = false;
   int last_src = 0;
   int split_len = 0;             // ratings per split-K chunk (0: no split)
+  bool tiers = false;            // degree tiers D = 48 / D = 80 in the row layout (rank_layout)
   int slab_blocks = 0;
   hipEvent_t ev[8] = {};
   hipStream_t st2 = nullptr;     // world > 1: factor-chunk gathers behind the solve

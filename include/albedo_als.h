@@ -61,7 +61,14 @@ typedef struct als_params {
   int32_t device;          /* HIP device ordinal; -1 = current device */
   int32_t light_max_degree;/* rows with <= this many ratings take the rotated push-through solve (capped at
                               96 at rank 65..128, 64 otherwise);
-                              -1 = engine default, 0 = every row takes the explicit Cholesky solve */
+                              -1 = engine default, 0 = every row takes the explicit Cholesky solve.
+                              The default limit is 64 at rank 65..256 and 32 below.  At rank 65..128 the
+                              default (-1, not nonnegative) also switches on the degree tiers: rows of
+                              33..48 ratings use a 48-wide instance of the push-through kernel, and rows of
+                              65..80 ratings, which stay above the limit, are solved by an 80-wide instance
+                              instead of the explicit solve.  A value >= 0 gives exactly the routing it
+                              names (no tiers); ALBEDO_DEGREE_TIERS=0 in the environment switches the tiers
+                              off for the default too. */
 } als_params;
 
 typedef struct als_ctx als_ctx;
@@ -212,7 +219,10 @@ enum {
 };
 int als_last_timings(const als_ctx* ctx, int dst_side, double* out, int n);
 /* Rows / nnz handled by each solve path in the last half-sweep of dst_side:
- * out[0]=light rows, out[1]=light nnz, out[2]=heavy rows, out[3]=heavy nnz.  With nonnegative =
+ * out[0]=light rows, out[1]=light nnz, out[2]=heavy rows, out[3]=heavy nnz.  "Light" means within
+ * the light limit (light_max_degree; 64 by default at rank 65..256) and solved by the push-through
+ * path; every row above the limit counts under out[2..3], the degree tier 65..80 included although a
+ * push-through instance solves it (its launch is timed with ALS_T_SOLVE_HEAVY).  With nonnegative =
  * true "light" is the lockstep NNLS kernel (16 low-degree rows per workgroup) and "heavy" every
  * other row (one workgroup per row). */
 int als_path_stats(const als_ctx* ctx, int dst_side, int64_t* out4);

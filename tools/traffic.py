@@ -29,6 +29,11 @@ def per_kernel(path, counter):
             base = m.group(1) if m else k.split("<")[0]
             tot[base] += float(r["Counter_Value"])
             nd[base].add(r["Dispatch_Id"])
+            # the push-through instances also one by one ("solve_light<128, 80>": the degree tiers)
+            inst = re.search(r"solve_light_kernel(<[0-9, ]+>)", k)
+            if inst:
+                tot[base + inst.group(1)] += float(r["Counter_Value"])
+                nd[base + inst.group(1)].add(r["Dispatch_Id"])
     return tot, {k: len(v) for k, v in nd.items()}
 
 
