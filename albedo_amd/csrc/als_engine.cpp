@@ -1,13 +1,15 @@
-// libalbedo_als.so host engine: the C ABI of include/albedo_als.h, except top-k and NDCG
-// (topk_host.cpp; engine.h is what the two files share).
+// libalbedo_als.so host engine: contexts, ingest, factor initialisation and the C ABI of
+// include/albedo_als.h, except top-k and NDCG (topk_host.cpp) and the held-out pair ranking
+// (eval_host.cpp).  The half-sweep and the row layout it runs over are in sweep_host.cpp; engine.h is
+// what the files share.
 //
 // Mirrors Spark MLlib 2.2.0 ALS.train as reached from ALSRecommenderBuilder.scala:46-58:
 //   userFactors = initialize(...); itemFactors = initialize(...)
 //   for iter in 1..maxIter: itemFactors = computeFactors(userFactors -> items)
 //                           userFactors = computeFactors(itemFactors -> users)
-// Each computeFactors call is one half-sweep here (half_sweep()):
+// Each computeFactors call is one half-sweep here (sweep_host.cpp half_sweep()):
 //   G = Σ y yᵀ over the src rows (MFMA, fp64 partials)    [+ all-reduce across ranks]
-//   G = P Λ Pᵀ (host fp64 eigensolver);  Z = X_src · P    [+ all-gather of the Z shard]
+//   G = P Λ Pᵀ (device fp64 eigensolver);  Z = X_src · P  (every rank rotates the gathered src)
 //   every dst row solved in the eigenbasis (light: push-through, heavy: explicit Cholesky)
 // Factors are stored in a per-side basis B (original = X · Bᵀ); solving from src basis B_s with
 // rotation P puts the dst solution in basis B_s·P, so only one rotation GEMM runs per half-sweep.
@@ -45,18 +47,12 @@ int albedo::fail(int code, const std::string& msg) {
   return code;
 }
 
-#define NCCLCHK(x)                                                                                 \
-  do {                                                                                             \
-    ncclResult_t r_ = (x);                                                                         \
-    if (r_ != ncclSuccess) return fail(ALS_E_RCCL, std::string("RCCL error: ") + ncclGetErrorString(r_) + " in " #x); \
-  } while (0)
-
 int albedo::set_device(als_ctx* c) {
   HIPCHK(hipSetDevice(c->dev));
   return ALS_OK;
 }
 
-// Copies and fills between the host and the context's buffers go through the engine stream c->st and
+// Copies between the host and the context's buffers go through the engine stream c->st and
 // complete before returning.  c->st is a non-blocking stream: it does not order itself after the null
 // stream, so a plain hipMemcpy / hipMemset could overlap the engine's kernels (a host-to-device
 // hipMemcpy from pageable memory may return before its DMA lands, a device-to-device one does not
@@ -67,22 +63,16 @@ hipError_t albedo::copy_st(const als_ctx* c, void* dst, const void* src, size_t 
   return e != hipSuccess ? e : hipStreamSynchronize(c->st);
 }
 
-namespace {
-
-hipError_t fill_st(const als_ctx* c, void* dst, int v, size_t bytes) {
-  if (bytes == 0) return hipSuccess;
-  const hipError_t e = hipMemsetAsync(dst, v, bytes, c->st);
-  return e != hipSuccess ? e : hipStreamSynchronize(c->st);
-}
-
 // world > 1: the factor-chunk gathers of the last half-sweep run on st2 behind the solve.  Anything
 // that rewrites factor buffers with default-stream copies, or returns to the caller as "done",
 // first waits for both streams.
-int drain(als_ctx* c) {
+int albedo::drain(als_ctx* c) {
   if (c->st2) HIPCHK(hipStreamSynchronize(c->st2));
   if (c->st) HIPCHK(hipStreamSynchronize(c->st));
   return ALS_OK;
 }
+
+namespace {
 
 int validate(const als_params* p) {
   auto bad = [](const char* name, double v) {
@@ -98,71 +88,6 @@ int validate(const als_params* p) {
   if (p->num_item_blocks < 1) return bad("numItemBlocks", p->num_item_blocks);
   if (padded_rank(p->rank) == 0)
     return fail(ALS_E_UNSUPPORTED, "rank " + std::to_string(p->rank) + " exceeds the compiled maximum (256)");
-  return ALS_OK;
-}
-
-// Rows of degree <= light_limit take the push-through solve (a d x d system).  d <= 64 by default;
-// light_max_degree up to 96 (KP = 128) routes rows of degree 65..96 through the d x d path too
-// (solve_light_kernel<128, 96>), measured against the explicit k x k wave kernel in DESIGN §4.
-// The limit is also what als_path_stats calls "light"; the degree tiers below do not move it.
-int64_t light_limit(const als_ctx* c) {
-  if (c->p.light_max_degree >= 0) return std::min<int64_t>(c->p.light_max_degree, c->KP == 128 ? 96 : 64);
-  return c->KP >= 128 ? 64 : 32;
-}
-
-// Degree tiers (KP = 128, the default light limit, Cholesky path): rows of degree 33..48 take
-// solve_light_kernel<128, 48> (3 panels, 6 tiles instead of 4 and 10) and rows of degree 65..80, which
-// are above the light limit, take solve_light_kernel<128, 80> at three waves per SIMD instead of the
-// wave kernel.  An explicit light_max_degree keeps the routing it names.
-// ALBEDO_DEGREE_TIERS=0 switches the tiers off (the A/B handle, read when the row layout is built).
-bool degree_tiers_on(const als_ctx* c) {
-  if (c->KP != 128 || c->p.light_max_degree != -1 || c->p.nonnegative) return false;
-  const char* e = std::getenv("ALBEDO_DEGREE_TIERS");
-  return !(e && *e && std::atoi(e) == 0);
-}
-
-int bucket_of(int64_t d, int64_t lmax, bool tiers) {
-  if (d <= lmax) {
-    if (d <= 16) return B_L16;
-    if (d <= 32) return B_L32;
-    if (tiers && d <= 48) return B_L48;
-    return d <= 64 ? B_L64 : B_L96;
-  }
-  return (tiers && d <= 80) ? B_M80 : B_HEAVY;
-}
-
-// ---- collectives ------------------------------------------------------------------------------
-int allreduce_G(als_ctx* c) {
-  const int64_t n = (int64_t)c->KP * c->KP;
-  if (c->world == 1) return ALS_OK;
-  if (c->comm) {
-    NCCLCHK(ncclAllReduce(c->d_G.p, c->d_G.p, n, ncclDouble, ncclSum, c->comm, c->st));
-    return ALS_OK;
-  }
-  std::vector<double> h(n);
-  HIPCHK(hipMemcpyAsync(h.data(), c->d_G.p, n * 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  if (c->h_allreduce(c->h_user, h.data(), n) != 0) return fail(ALS_E_RCCL, "host all-reduce callback failed");
-  HIPCHK(hipMemcpyAsync(c->d_G.p, h.data(), n * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return ALS_OK;
-}
-
-// in-place all-gather on stream s: rank r's rows_per_rank rows at buf + r·rows_per_rank·KP
-int allgather_rows(als_ctx* c, float* buf, int64_t rows_per_rank, hipStream_t s) {
-  if (c->world == 1) return ALS_OK;
-  const int64_t per = rows_per_rank * c->KP;
-  if (c->comm) {
-    NCCLCHK(ncclAllGather(buf + (int64_t)c->rank * per, buf, per, ncclFloat, c->comm, s));
-    return ALS_OK;
-  }
-  std::vector<float> h((size_t)per * c->world);
-  HIPCHK(hipMemcpyAsync(h.data() + (size_t)c->rank * per, buf + (int64_t)c->rank * per, per * 4,
-                        hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (c->h_allgather(c->h_user, h.data(), per) != 0) return fail(ALS_E_RCCL, "host all-gather callback failed");
-  HIPCHK(hipMemcpyAsync(buf, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));
   return ALS_OK;
 }
 
@@ -188,212 +113,9 @@ int albedo::allgather_host(als_ctx* c, float* buf, int64_t n) {
 
 namespace {
 
-// Gathers layout chunks [q0, q1) of the own rows `own` ([nch·chpad][KP], zero past own_n) into
-// `full` ([prows][KP]) on stream s: chunk q of every rank is one contiguous all-gather.
-int gather_chunks(als_ctx* c, const Side& S, const float* own, float* full, int q0, int q1, hipStream_t s) {
-  const int64_t per = S.chpad * c->KP;
-  for (int q = q0; q < q1; ++q) {
-    float* base = full + (int64_t)q * c->world * per;
-    HIPCHK(hipMemcpyAsync(base + (int64_t)c->rank * per, own + (int64_t)q * per, per * 4, hipMemcpyDeviceToDevice, s));
-    TRYC(allgather_rows(c, base, S.chpad, s));
-  }
-  return ALS_OK;
-}
-
-// Ratings per split-K chunk.  One workgroup gathering a 10^6-star row is the launch's tail (45.9
-// ms for 1.05M stars at rank 128, more than a whole c4 half-sweep at 8 GPUs), and a partial of 8192
-// ratings keeps every fp32 MFMA accumulation to 256 steps before the fp64 sum (a 1.05M-star row then
-// matches the fp64 solve to 7e-7, tests/test_gpu_heavy_tail.py).  ALBEDO_SPLIT_CHUNK overrides it
-// for tuning (0 disables the split): 2048 / 4096 / 16384 measured 338 / 324 / 311 ms per c4 sweep
-// against 316 ms.
-int split_chunk_len() {
-  const char* e = std::getenv("ALBEDO_SPLIT_CHUNK");
-  if (e && *e) return std::max(0, std::atoi(e));
-  return 8192;
-}
-
-// nonnegative = true: light rows run in lockstep (nnls_batch.hip), BATCH_SLOTS[v] rows per workgroup
-// for degrees up to nnls_batch_max_degree(KP, slots).  A lockstep iteration costs about the same for
-// any slot count, so the variants pay off down to 8 slots (KP = 256 per row-iteration, tools/probe/
-// batchtime: 16 slots 1.3 us, 8 slots 2.2 us, 4 slots 4.7 us against 4.5 us for solve_nnls_kernel);
-// rows of higher degree take solve_nnls_kernel.
-constexpr int BATCH_SLOTS[5] = {16, 8, 4, 2, 1};
-constexpr int BATCH_MIN_SLOTS = 8;
-int nnls_min_slots() {  // ALBEDO_NNLS_MIN_SLOTS: A/B knob (16, 8, 4, 2 or 1)
-  const char* e = std::getenv("ALBEDO_NNLS_MIN_SLOTS");
-  const int v = e && *e ? std::atoi(e) : BATCH_MIN_SLOTS;
-  return (v == 16 || v == 8 || v == 4 || v == 2 || v == 1) ? v : BATCH_MIN_SLOTS;
-}
-int64_t nnls_batch_rows_limit(const als_ctx* c, int v) {
-  if (BATCH_SLOTS[v] < nnls_min_slots()) return 0;
-  return std::min<int64_t>(nnls_batch_max_degree(c->KP, BATCH_SLOTS[v]), light_limit(c));
-}
-
 // world > 1: the solve runs in this many row chunks, each gathered on a second stream while the
 // next one solves
 int gather_chunk_count() { return 4; }
-
-// Heavy rows at padded rank <= 128 run one wave per row (heavy_wave.hip); rank 256 uses the 4-wave
-// workgroup kernel (solve_heavy_kernel).
-bool use_wave_kernel(const als_ctx* c);
-
-int factor_buffers(als_ctx* c);
-
-// Everything that depends on the rank / light-row limit rather than on the ratings: degree buckets
-// (the light limit follows KP), split-K lists, then factor_buffers.  Called after ingest and again by
-// als_set_params, so several fits (a CV grid) share one ingest.
-int rank_layout(als_ctx* c) {
-  TRYC(drain(c));
-  const int64_t lmax = light_limit(c);
-  c->split_len = split_chunk_len();
-  c->tiers = degree_tiers_on(c);
-  for (int side = 0; side < 2; ++side) {
-    Side& S = c->s[side];
-    // degree buckets (heavy rows longest first for the tail)
-    std::vector<int32_t> rows[NBUCKET];
-    for (int b = 0; b < NBUCKET; ++b) S.bnnz[b] = 0;
-    for (int64_t r = 0; r < S.own_n; ++r) {
-      const int b = bucket_of(S.h_deg[r], lmax, c->tiers);
-      rows[b].push_back((int32_t)r);
-      S.bnnz[b] += S.h_deg[r];
-    }
-    std::stable_sort(rows[B_HEAVY].begin(), rows[B_HEAVY].end(),
-                     [&](int32_t a, int32_t b) { return S.h_deg[a] > S.h_deg[b]; });
-    S.n_batch = S.n_batch_nnz = 0;
-    for (int v = 0; v < 6; ++v) S.bat_off[v] = 0;
-    if (c->p.nonnegative) {  // light rows by ascending degree: the lockstep NNLS kernel's rows first
-      for (int b = 0; b < B_HEAVY; ++b)
-        std::stable_sort(rows[b].begin(), rows[b].end(), [&](int32_t x, int32_t y) { return S.h_deg[x] < S.h_deg[y]; });
-      // variant v takes the degrees (limit of v-1, limit of v]; the light list is one ascending run
-      int64_t pos = 0;
-      std::vector<int32_t> light;
-      for (int b = 0; b < B_HEAVY; ++b) light.insert(light.end(), rows[b].begin(), rows[b].end());
-      for (int v = 0; v < 5; ++v) {
-        const int64_t dl = nnls_batch_rows_limit(c, v);
-        while (pos < (int64_t)light.size() && S.h_deg[light[pos]] <= dl) S.n_batch_nnz += S.h_deg[light[pos++]];
-        S.bat_off[v + 1] = pos;
-      }
-      S.n_batch = pos;
-    }
-    // world > 1 (Cholesky path): each bucket's rows grouped by solve chunk (= gathered-layout
-    // chunk, local row / chpad), stably, so a chunk's rows of a bucket are one contiguous run
-    const int nsolve = (c->world > 1 && !c->p.nonnegative) ? S.nch : 1;
-    S.nsolve = nsolve;
-    auto chunk_of = [&](int32_t r) { return nsolve == 1 ? 0 : (int)std::min<int64_t>(r / S.chpad, nsolve - 1); };
-    std::vector<int32_t> all;
-    all.reserve(S.own_n);
-    for (int b = 0; b < NBUCKET; ++b) {
-      S.boff[b] = (int64_t)all.size();
-      // grouped by solve chunk; B_L16: within a chunk the rows of degree <= 8 first (light16 pairs them)
-      const bool pairs = b == B_L16;
-      std::stable_sort(rows[b].begin(), rows[b].end(), [&](int32_t x, int32_t y) {
-        const int cx = chunk_of(x), cy = chunk_of(y);
-        if (cx != cy || !pairs) return cx < cy;
-        return (S.h_deg[x] <= 8) > (S.h_deg[y] <= 8);
-      });
-      int64_t p = 0;
-      for (int q = 0; q <= nsolve; ++q) {
-        while (q < nsolve && p < (int64_t)rows[b].size() && chunk_of(rows[b][p]) < q) ++p;
-        S.cb[b][q] = S.boff[b] + (q == nsolve ? (int64_t)rows[b].size() : p);
-      }
-      if (pairs)
-        for (int q = 0; q < nsolve; ++q) {
-          int64_t k = 0;
-          for (int64_t i = S.cb[b][q] - S.boff[b]; i < S.cb[b][q + 1] - S.boff[b] && S.h_deg[rows[b][i]] <= 8; ++i) ++k;
-          S.c8[q] = k;
-        }
-      all.insert(all.end(), rows[b].begin(), rows[b].end());
-    }
-    S.boff[NBUCKET] = (int64_t)all.size();
-    HIPCHK(S.d_rows.ensure(all.size() * 4));
-    HIPCHK(copy_st(c, S.d_rows.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(S.d_desc.ensure(all.size() * 16));
-    HIPCHK(launch_row_desc(S.d_rows.as<int32_t>(), (int64_t)all.size(), S.d_ptr.as<int64_t>(), S.d_desc.as<int32_t>(), c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    // split-K chunks of each solve chunk's heaviest rows (a prefix of its heavy run: by degree);
-    // slot0 is chunk-local (starts at 0 for every solve chunk)
-    const int64_t CH = c->split_len;
-    std::vector<int32_t> crow, cidx, slot0;
-    S.n_split = 0;
-    for (int q = 0; q < nsolve; ++q) {
-      S.ck_off[q] = (int64_t)crow.size();
-      S.sl_off[q] = (int64_t)slot0.size();
-      slot0.push_back(0);
-      int64_t n = 0;
-      for (int64_t p = S.cb[B_HEAVY][q]; p < S.cb[B_HEAVY][q + 1]; ++p) {
-        const int32_t r = all[p];
-        if (CH <= 0 || S.h_deg[r] <= CH) break;
-        const int64_t nch = (S.h_deg[r] + CH - 1) / CH;
-        for (int64_t k = 0; k < nch; ++k) {
-          crow.push_back(r);
-          cidx.push_back((int32_t)k);
-        }
-        slot0.push_back((int32_t)((int64_t)crow.size() - S.ck_off[q]));
-        ++n;
-      }
-      S.split_n[q] = n;
-      S.n_split += n;
-    }
-    S.ck_off[nsolve] = (int64_t)crow.size();
-    S.n_chunks = (int64_t)crow.size();
-    if (S.n_split > 0) {
-      HIPCHK(S.d_chunk_row.ensure(crow.size() * 4));
-      HIPCHK(S.d_chunk_idx.ensure(cidx.size() * 4));
-      HIPCHK(S.d_slot0.ensure(slot0.size() * 4));
-      HIPCHK(copy_st(c, S.d_chunk_row.p, crow.data(), crow.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(copy_st(c, S.d_chunk_idx.p, cidx.data(), cidx.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(copy_st(c, S.d_slot0.p, slot0.data(), slot0.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
-  return factor_buffers(c);
-}
-
-// Per-fit device state: split-K records, factor / rotated-factor buffers, Gram slabs and scratch;
-// the factors are dropped (the next fit initialises them).
-int factor_buffers(als_ctx* c) {
-  {
-    const size_t rec = (size_t)split_rec_floats(c->KP) * 4;
-    const int64_t mc = std::max(c->s[0].n_chunks, c->s[1].n_chunks);
-    const int64_t ms = std::max(c->s[0].n_split, c->s[1].n_split);
-    if (mc > 0) {
-      HIPCHK(c->d_partial.ensure(mc * rec));
-      HIPCHK(c->d_reduced.ensure(ms * rec));
-    }
-  }
-  for (int side = 0; side < 2; ++side) {
-    Side& S = c->s[side];
-    // X padded to whole layout chunks (zero rows past own_n: they travel in the chunk gathers)
-    HIPCHK(S.d_X.ensure((size_t)std::max<int64_t>(std::max<int64_t>(S.own_n, (int64_t)S.nch * S.chpad), 1) * c->KP * 4));
-    // + one zero row at prows(): the gather target of masked light-row entries (never written)
-    HIPCHK(S.d_Z.ensure((size_t)(S.prows() + 1) * c->KP * 4));
-    HIPCHK(fill_st(c, S.d_X.p, 0, S.d_X.bytes));
-    HIPCHK(fill_st(c, S.d_Z.p, 0, S.d_Z.bytes));
-    if (c->world > 1) {
-      HIPCHK(S.d_Xfull.ensure((size_t)std::max<int64_t>(S.prows(), 1) * c->KP * 4));
-      HIPCHK(fill_st(c, S.d_Xfull.p, 0, S.d_Xfull.bytes));
-    }
-    S.full_valid = false;
-    HIPCHK(S.d_B.ensure((size_t)c->KP * c->KP * 8));
-    HIPCHK(S.d_Gk.ensure((size_t)c->KP * c->KP * 8));
-    HIPCHK(S.d_GB.ensure((size_t)c->KP * c->KP * 8));
-    HIPCHK(launch_identity(S.d_B.as<double>(), c->KP, c->st));
-    S.has_gram = false;
-    S.has_factors = false;
-    S.orig_valid = false;
-    S.full_valid = false;
-  }
-  const int64_t maxsrc = std::max(c->s[0].own_n, c->s[1].own_n);
-  c->slab_blocks = gram_slab_blocks(c->KP, maxsrc);
-  HIPCHK(c->slab.ensure(gram_slab_doubles(c->KP, c->slab_blocks) * 8));
-  HIPCHK(c->d_G.ensure((size_t)c->KP * c->KP * 8));
-  HIPCHK(c->d_P.ensure((size_t)c->KP * c->KP * 4));
-  HIPCHK(c->d_eig.ensure(eig_scratch_doubles(c->KP) * 8));
-  HIPCHK(c->d_lam.ensure((size_t)c->KP * 4));
-  HIPCHK(c->d_err.ensure(16));
-  HIPCHK(c->d_cs.ensure((size_t)2 * c->KP * 4));
-  HIPCHK(c->d_csmax.ensure((size_t)c->KP * 4));
-  return ALS_OK;
-}
 
 // ---- ingest -------------------------------------------------------------------------------------
 // A fork views its parent's ingest, and a parent's ingest is viewed by its live forks: neither may
@@ -532,17 +254,6 @@ int spark_init(als_ctx* c) {
   return ALS_OK;
 }
 
-// the solve paths named by the bits of a not-positive-definite flag word (kernels.h ALBEDO_EF_*)
-std::string err_paths(int err) {
-  std::string r;
-  const std::pair<int, const char*> names[] = {{ALBEDO_EF_LIGHT16, "light16"}, {ALBEDO_EF_LIGHT_REG, "light-d16"},
-                                               {ALBEDO_EF_LIGHT_ACC, "light"}, {ALBEDO_EF_WAVE, "wave"},
-                                               {ALBEDO_EF_HEAVY, "heavy"}};
-  for (const auto& n : names)
-    if (err & n.first) r += std::string(r.empty() ? ": " : ",") + n.second;
-  return r;
-}
-
 }  // namespace
 
 float albedo::event_ms(hipEvent_t a, hipEvent_t b) {
@@ -550,449 +261,6 @@ float albedo::event_ms(hipEvent_t a, hipEvent_t b) {
   (void)hipEventElapsedTime(&ms, a, b);
   return ms;
 }
-
-namespace {
-
-// fp16 column scales of the heavy build for dst side T over the gathered src rows Z
-// have_max: the rotation left the column maxima of Z in d_csmax (rotate_kernel's epilogue)
-int column_scales(als_ctx* c, const Side& S, const Side& T, bool have_max = false) {
-  const float cmax = c->p.implicit_prefs ? (float)c->p.alpha * T.vmax : 1.0f;
-  HIPCHK(launch_colscale(c->KP, S.d_Z.as<float>(), S.prows(), cmax, c->d_csmax.as<unsigned>(),
-                         c->d_cs.as<float>(), c->st, have_max));
-  return ALS_OK;
-}
-
-int heavy_launches(als_ctx* c, const Side& T, SolveArgs a, int64_t h0, int64_t hn, bool nnls, int q = 0);
-bool use_wave_kernel(const als_ctx* c);
-
-// KP = 128: the rotation on bf16 MFMA with the fused operand split (rotate_bf); KP = 64 / 256 keep the
-// fp32 MFMA rotation + colmax epilogue + separate presplit pass
-bool rotate_bf_on(const als_ctx* c) { return c->KP == 128; }
-
-// One confidence c for every rating of dst side T (explicit: c = 1; implicit: all |r| equal): the
-// heavy build's operand split z·√c·colscale -> fp16 hi + lo is then the same for every gather of a
-// src row, so it runs once per src row here (launch_presplit) instead of once per gathered rating
-// inside the wave kernel.
-// presplit_wanted: whether the split applies to this half (and its √c); split_done: the rotation
-// already wrote it (rotate_bf)
-bool presplit_wanted(const als_ctx* c, const Side& T, float* sw) {
-  const bool uniform = !c->p.implicit_prefs || (T.vmin == T.vmax && T.vmax > 0.f);
-  // rows above the light limit: B_M80 counts, since a forced-heavy half sends it to the wave kernel
-  if (!uniform || !use_wave_kernel(c) || T.boff[NBUCKET] == T.boff[B_LIGHT_END]) return false;
-  const float cw = c->p.implicit_prefs ? (float)c->p.alpha * T.vmax : 1.0f;
-  if (!(cw > 0.f)) return false;
-  *sw = std::sqrt(cw);
-  return true;
-}
-
-int presplit(als_ctx* c, const Side& S, const Side& T, const void** zhl, float* wsc, float* inv_sw,
-             bool split_done = false) {
-  *zhl = nullptr;
-  float sw = 1.f;
-  if (!presplit_wanted(c, T, &sw)) return ALS_OK;
-  const float cw = c->p.implicit_prefs ? (float)c->p.alpha * T.vmax : 1.0f;
-  HIPCHK(c->d_Zhl.ensure((size_t)(S.prows() + 1) * c->KP * 4));
-  if (!split_done)
-    HIPCHK(launch_presplit(c->KP, S.d_Z.as<float>(), S.prows(), c->d_cs.as<float>(), sw, c->d_Zhl.p, c->st));
-  // b' weights w = 1 + c (implicit, r > 0) or r (explicit), scaled by a power of two below 2^13
-  const double wmax = c->p.implicit_prefs ? 1.0 + (double)cw : (double)T.vmax;
-  int e = 0;
-  std::frexp(wmax > 0.0 ? wmax : 1.0, &e);  // wmax < 2^e
-  *wsc = (float)std::ldexp(1.0, std::max(-60, std::min(60, 13 - e)));
-  *inv_sw = 1.0f / sw;
-  *zhl = c->d_Zhl.p;
-  return ALS_OK;
-}
-
-// nonnegative = true: Spark's NNLSSolver in the original basis (no rotation; B stays I)
-int half_sweep_nnls(als_ctx* c, int t) {
-  const int sidx = 1 - t;
-  Side& S = c->s[sidx];
-  Side& T = c->s[t];
-  const int KP = c->KP, k = c->p.rank;
-  hipStream_t st = c->st;
-  hipEvent_t* ev = c->ev;
-  const int ngt = nnls_gtile_floats(KP);
-  std::vector<float> gt(ngt, 0.f);
-  float gscale = 1.0f;
-  if (c->p.implicit_prefs) {
-    HIPCHK(launch_gram(KP, S.d_X.as<float>(), S.own_n, c->slab.as<double>(), c->slab_blocks, c->d_G.as<double>(), st));
-    TRYC(allreduce_G(c));
-    std::vector<double> Gf((size_t)KP * KP);
-    HIPCHK(hipMemcpyAsync(Gf.data(), c->d_G.p, Gf.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(S.d_Gk.p, c->d_G.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(S.d_GB.p, S.d_B.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    S.has_gram = true;
-    for (int i = 0; i < KP; ++i)
-      for (int j = 0; j < 16 * ((i >> 4) + 1); ++j) gt[nnls_gtile_index(i, j)] = (float)Gf[(size_t)i * KP + j];
-    double gmax = 0.0;
-    for (double v : Gf) gmax = std::max(gmax, std::fabs(v));
-    if (gmax > 0.0) {  // lockstep kernel's fp16 split of G: max|G|·gscale < 2^15
-      int ex = 0;
-      (void)std::frexp(gmax, &ex);
-      gscale = (float)std::ldexp(1.0, std::max(-120, std::min(120, 15 - ex)));
-    }
-  }
-  HIPCHK(hipEventRecord(ev[1], st));
-  HIPCHK(c->d_Gt.ensure((size_t)ngt * 4));
-  HIPCHK(hipMemcpyAsync(c->d_Gt.p, gt.data(), (size_t)ngt * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(c->d_lam.p, 0, KP * 4, st));
-  HIPCHK(hipEventRecord(ev[2], st));
-  if (c->world == 1) HIPCHK(hipMemcpyAsync(S.d_Z.p, S.d_X.p, (size_t)S.own_n * KP * 4, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipEventRecord(ev[3], st));
-  if (c->world > 1) TRYC(gather_chunks(c, S, S.d_X.as<float>(), S.d_Z.as<float>(), 0, S.nch, st));
-  HIPCHK(hipEventRecord(ev[4], st));
-  HIPCHK(hipMemsetAsync(c->d_err.p, 0, 4, st));
-  TRYC(column_scales(c, S, T));
-  HIPCHK(hipEventRecord(ev[5], st));
-  SolveArgs a{};
-  a.Z = S.d_Z.as<float>();
-  a.ptr = T.d_ptr.as<int64_t>();
-  a.col = T.d_col.as<int32_t>();
-  a.val = T.d_val.as<float>();
-  a.lam = c->d_lam.as<float>();
-  a.X = T.d_X.as<float>();
-  a.kreal = k;
-  a.implicit = c->p.implicit_prefs;
-  a.alpha = (float)c->p.alpha;
-  a.reg = (float)c->p.reg_param;
-  a.err = c->d_err.as<int>();
-  a.colscale = c->d_cs.as<float>();
-  HIPCHK(c->d_iters.ensure(32));  // [sum, max] of every row, then [sum, max] of the lockstep rows
-  HIPCHK(hipMemsetAsync(c->d_iters.p, 0, 32, st));
-  a.iters = c->d_iters.as<unsigned long long>();
-  const int64_t nb = std::min<int64_t>(T.n_batch, T.boff[B_HEAVY]);
-  if (nb > 0) {
-    HIPCHK(c->d_gfrag.ensure((size_t)KP * KP * 4));
-    HIPCHK(c->d_counter.ensure(64));
-    HIPCHK(launch_nnls_gfrag(KP, c->d_Gt.as<float>(), gscale, c->d_gfrag.p, st));
-    // ALBEDO_NNLS_BATCH_WGS caps the persistent grid (tests: force many slot refills per workgroup)
-    const char* ew = std::getenv("ALBEDO_NNLS_BATCH_WGS");
-    const int wgs = (ew && std::atoi(ew) > 0) ? std::min(c->n_cu, std::atoi(ew)) : c->n_cu;
-    for (int v = 0; v < 5; ++v) {
-      SolveArgs b = a;
-      b.rows = T.d_rows.as<int32_t>() + T.bat_off[v];
-      b.n_rows = T.bat_off[v + 1] - T.bat_off[v];
-      b.iters = a.iters + 2;
-      HIPCHK(launch_nnls_batch(KP, BATCH_SLOTS[v], b, c->d_gfrag.p, gscale, c->d_counter.as<unsigned int>(), wgs, st));
-    }
-  }
-  HIPCHK(hipEventRecord(ev[7], st));
-  TRYC(heavy_launches(c, T, a, nb, T.boff[B_HEAVY] - nb, true));
-  TRYC(heavy_launches(c, T, a, T.boff[B_HEAVY], T.boff[NBUCKET] - T.boff[B_HEAVY], true));
-  a.n_rows = T.boff[NBUCKET];
-  T.stats[0] = nb;  // the lockstep kernel's rows and stars, then every other row
-  T.stats[1] = nb > 0 ? T.n_batch_nnz : 0;
-  T.stats[2] = a.n_rows - T.stats[0];
-  T.stats[3] = T.own_nnz - T.stats[1];
-  HIPCHK(hipEventRecord(ev[6], st));
-  int err = 0;
-  unsigned long long it[4] = {0, 0, 0, 0};
-  HIPCHK(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(it, c->d_iters.p, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  T.solver[0] = (int64_t)(it[0] + it[2]);
-  T.solver[1] = (int64_t)std::max(it[1], it[3]);
-  T.solver[2] = T.boff[NBUCKET];
-  T.solver[3] = (int64_t)it[2];
-  T.t[ALS_T_GRAM] = event_ms(ev[0], ev[1]);
-  T.t[ALS_T_EIG] = 0.0;
-  T.t[ALS_T_ROTATE] = event_ms(ev[2], ev[3]);
-  T.t[ALS_T_COMM] = event_ms(ev[3], ev[4]);
-  T.t[ALS_T_SOLVE_LIGHT] = event_ms(ev[5], ev[7]);  // lockstep kernel
-  T.t[ALS_T_SOLVE_HEAVY] = event_ms(ev[7], ev[6]);  // per-row kernels (split-K included)
-  T.t[ALS_T_HALF_TOTAL] = event_ms(ev[0], ev[6]);
-  if (err & 4) return fail(ALS_E_STATE, "lockstep NNLS row above its degree limit (row layout out of date)");
-  if (err) return fail(ALS_E_NOT_POSITIVE_DEFINITE, "NNLS solve produced a non-finite result");
-  HIPCHK(hipMemcpyAsync(T.d_B.p, S.d_B.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));  // no rotation
-  T.has_factors = true;
-  T.orig_valid = false;
-  T.full_valid = false;
-  return ALS_OK;
-}
-
-// Heavy launch over rows [h0, h0 + hn) of T's bucket-ordered row list, the first split_n[q] of which
-// (when h0 starts solve chunk q's heavy run) are the split-K rows: chunk partials + fp64 reduce, then
-// the factor (or NNLS) from the reduced records, then the remaining rows as usual.
-int heavy_launches(als_ctx* c, const Side& T, SolveArgs a, int64_t h0, int64_t hn, bool nnls, int q) {
-  const int KP = c->KP;
-  const int32_t* rows = T.d_rows.as<int32_t>();
-  int64_t ns = (h0 == T.cb[B_HEAVY][q]) ? std::min<int64_t>(T.split_n[q], hn) : 0;
-  if (ns > 0) {
-    SplitArgs sp{};
-    sp.chunk_row = T.d_chunk_row.as<int32_t>() + T.ck_off[q];
-    sp.chunk_idx = T.d_chunk_idx.as<int32_t>() + T.ck_off[q];
-    sp.n_chunks = T.ck_off[q + 1] - T.ck_off[q];
-    sp.chunk_len = c->split_len;
-    sp.slot0 = T.d_slot0.as<int32_t>() + T.sl_off[q];
-    sp.n_split = ns;
-    sp.partial = c->d_partial.as<float>();
-    sp.reduced = c->d_reduced.as<float>();
-    HIPCHK(launch_heavy_split(KP, a, sp, use_wave_kernel(c), c->st));
-    SolveArgs b = a;
-    b.rows = rows + h0;
-    b.n_rows = ns;
-    b.prebuilt = c->d_reduced.as<float>();
-    if (nnls) HIPCHK(launch_solve_nnls(KP, b, c->d_Gt.as<float>(), c->st));
-    else HIPCHK(launch_solve_heavy(KP, b, c->st));
-  }
-  a.rows = rows + h0 + ns;
-  a.desc = T.d_desc.as<int32_t>() + 4 * (h0 + ns);  // the descriptors follow d_rows entry by entry
-  a.n_rows = hn - ns;
-  a.prebuilt = nullptr;
-  if (nnls) HIPCHK(launch_solve_nnls(KP, a, c->d_Gt.as<float>(), c->st));
-  else if (use_wave_kernel(c)) HIPCHK(launch_solve_wave(KP, a, c->st));
-  else HIPCHK(launch_solve_heavy(KP, a, c->st));
-  return ALS_OK;
-}
-
-bool use_wave_kernel(const als_ctx* c) { return c->KP <= 128; }
-
-// After a failed solve: what the half's inputs and outputs held (non-finite counts, first bad index,
-// max |value|), so a failure that does not repeat still names where it started
-std::string failure_diag(als_ctx* c, const Side& S, const Side& T, int64_t ns, const void* zhl) {
-  const int KP = c->KP;
-  struct Item {
-    const char* name;
-    const void* p;
-    int64_t n;
-    bool f16;
-  } items[] = {{"src X", S.d_X.p, S.own_n * KP, false},
-               {"src Z", S.d_Z.p, ns * KP, false},
-               {"Z zero row", S.d_Z.as<float>() + S.prows() * KP, KP, false},
-               {"Zhl", zhl, zhl ? (S.prows() + 1) * KP * 2 : 0, true},
-               {"lam", c->d_lam.p, KP, false},
-               {"colscale", c->d_cs.p, KP, false},
-               {"dst X", T.d_X.p, T.own_n * KP, false}};
-  const int ni = (int)(sizeof(items) / sizeof(items[0]));
-  DevBuf out;
-  std::vector<unsigned long long> h((size_t)ni * 3, 0ull);
-  for (int i = 0; i < ni; ++i) h[(size_t)i * 3 + 1] = ~0ull;
-  // an early return drains the stream first: the queued upload reads h and the scans write out
-  auto unavailable = [&]() { (void)hipStreamSynchronize(c->st); return std::string(" [diagnostics unavailable]"); };
-  if (out.ensure(h.size() * 8) != hipSuccess ||
-      hipMemcpyAsync(out.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->st) != hipSuccess)
-    return unavailable();
-  for (int i = 0; i < ni; ++i)
-    if (items[i].p && launch_diag_scan(items[i].p, items[i].n, items[i].f16, out.as<unsigned long long>() + 3 * i, c->st) != hipSuccess)
-      return unavailable();
-  std::vector<float> lam(KP), cs(KP);
-  if (hipMemcpyAsync(h.data(), out.p, h.size() * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-      hipMemcpyAsync(lam.data(), c->d_lam.p, KP * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-      hipMemcpyAsync(cs.data(), c->d_cs.p, KP * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-      hipStreamSynchronize(c->st) != hipSuccess)
-    return unavailable();
-  std::string r = " [";
-  char buf[160];
-  for (int i = 0; i < ni; ++i) {
-    if (!items[i].p) continue;
-    const unsigned mx = (unsigned)h[(size_t)i * 3 + 2];
-    float fmx;
-    std::memcpy(&fmx, &mx, 4);
-    if (h[(size_t)i * 3])
-      std::snprintf(buf, sizeof buf, "%s: %llu non-finite (first at %llu, row %llu), max %.3g; ", items[i].name,
-                    h[(size_t)i * 3], h[(size_t)i * 3 + 1], h[(size_t)i * 3 + 1] / (items[i].f16 ? 2 * KP : KP), fmx);
-    else std::snprintf(buf, sizeof buf, "%s: finite, max %.3g; ", items[i].name, fmx);
-    r += buf;
-  }
-  const auto lm = std::minmax_element(lam.begin(), lam.begin() + c->p.rank);
-  const auto cm = std::minmax_element(cs.begin(), cs.begin() + c->p.rank);
-  std::snprintf(buf, sizeof buf, "lam %.4g..%.4g, colscale %.4g..%.4g]", *lm.first, *lm.second, *cm.first, *cm.second);
-  return r + buf;
-}
-
-int half_sweep(als_ctx* c, int t) {
-  const int sidx = 1 - t;
-  Side& S = c->s[sidx];
-  Side& T = c->s[t];
-  if (!S.has_factors) return fail(ALS_E_STATE, "source factors are not initialised");
-  const int KP = c->KP, k = c->p.rank;
-  hipStream_t st = c->st;
-  hipEvent_t* ev = c->ev;
-  const bool multi = c->world > 1;
-  bool have_cmax = false, cs_done = false, split_done = false;
-  bool force_heavy = c->p.light_max_degree == 0;
-  bool singular = false;  // regParam = 0 and min Λ <= 1e-12 max Λ
-  // world > 1: the previous half's factor gathers (second stream) finish before any collective or
-  // rotation of this one is issued -- two RCCL operations of one communicator must never overlap
-  if (multi) HIPCHK(hipStreamWaitEvent(st, c->evc[8], 0));
-  HIPCHK(hipEventRecord(ev[0], st));
-  if (c->p.nonnegative) return half_sweep_nnls(c, t);
-  if (multi && !S.full_valid) {  // src factors set outside a half-sweep (init / injection): gather now
-    TRYC(gather_chunks(c, S, S.d_X.as<float>(), S.d_Xfull.as<float>(), 0, S.nch, st));
-    S.full_valid = true;
-  }
-  if (c->p.implicit_prefs) {
-    HIPCHK(launch_gram(KP, S.d_X.as<float>(), S.own_n, c->slab.as<double>(), c->slab_blocks, c->d_G.as<double>(), st));
-    TRYC(allreduce_G(c));
-    HIPCHK(hipEventRecord(ev[1], st));
-    // eigenbasis of the src Gram on the device (eig.hip): warm-started cyclic Jacobi in fp64, no host
-    // round trip; the dst side's new basis B_t = B_s·P is formed there too
-    HIPCHK(hipMemcpyAsync(S.d_Gk.p, c->d_G.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(S.d_GB.p, S.d_B.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));
-    S.has_gram = true;
-    HIPCHK(launch_device_eig(KP, k, c->d_G.as<double>(), S.d_B.as<double>(), T.d_B.as<double>(), T.d_B.as<double>(),
-                             c->d_eig.as<double>(), c->d_P.as<float>(), c->d_lam.as<float>(), c->d_csmax.as<unsigned>(), st));
-    if (c->p.reg_param == 0.0) {
-      // the push-through light solve needs Λ + λn > 0 for every row; with λ = 0 a singular Gram sends
-      // every row to the explicit path (the only host round trip left, and only at regParam = 0)
-      double wmm[2] = {0.0, 0.0};
-      HIPCHK(hipMemcpyAsync(wmm, eig_minmax(c->d_eig.as<double>(), KP), 16, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (!(wmm[0] > 1e-12 * wmm[1])) force_heavy = singular = true;
-    }
-    HIPCHK(hipEventRecord(ev[2], st));
-    // world > 1: every rank rotates the whole gathered src (no collective on the critical path)
-    const float* Xs = multi ? S.d_Xfull.as<float>() : S.d_X.as<float>();
-    const int64_t ns = multi ? S.prows() : S.own_n;
-    // regParam = 0 on a near-singular Gram: nothing but Σ c z² stands on the diagonal of a small
-    // eigen-direction, and that bound's floor of 1e-6 λ_max is decades above its column of Z, whose fp16
-    // hi + lo split then keeps too few bits (1.3e-4 on a row at rank 128 with one src column at 2^-22).
-    // Such a half takes the fp32 rotation below, whose column scales come from the measured maxima.
-    if (rotate_bf_on(c) && !singular) {
-      // bf16 MFMA rotation with the heavy build's split in the same pass.  Its column scales come
-      // first, from a bound: Σ_i Z_ij² = p_jᵀ G p_j, which is λ_j up to the fp32 rounding of P and of
-      // the product (≤ 1e-6 λ_max), so max_i |Z_ij| ≤ √(λ_j + 1e-6 λ_max).  The split's fp16 range
-      // needs the scaled maxima below 2^16; the scales put the bound at 2^13 (colscale_kernel).
-      // (the bound itself came from the eigensolver: launch_device_eig left it in d_csmax)
-      TRYC(column_scales(c, S, T, true));
-      cs_done = true;
-      float sw = 1.f;
-      split_done = presplit_wanted(c, T, &sw);
-      if (split_done) HIPCHK(c->d_Zhl.ensure((size_t)(S.prows() + 1) * KP * 4));
-      HIPCHK(c->d_Pf.ensure((size_t)rotate_bf_pfrag_bytes(KP)));
-      HIPCHK(launch_rotate_bf(KP, Xs, c->d_P.as<float>(), c->d_Pf.p, S.d_Z.as<float>(), ns, c->d_cs.as<float>(), sw,
-                              split_done ? c->d_Zhl.p : nullptr, S.prows(), c->n_cu, st));
-    } else {
-      // the rotation also leaves the column maxima of Z for the heavy build's column scales
-      HIPCHK(hipMemsetAsync(c->d_csmax.p, 0, KP * sizeof(unsigned), st));
-      HIPCHK(launch_rotate(KP, Xs, c->d_P.as<float>(), S.d_Z.as<float>(), ns, st, c->d_csmax.as<unsigned>()));
-      have_cmax = true;
-    }
-  } else {
-    HIPCHK(hipEventRecord(ev[1], st));
-    HIPCHK(hipMemsetAsync(c->d_lam.p, 0, KP * 4, st));
-    HIPCHK(hipMemcpyAsync(T.d_B.p, S.d_B.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));
-    if (c->p.reg_param == 0.0) force_heavy = true;
-    HIPCHK(hipEventRecord(ev[2], st));
-    if (multi) HIPCHK(hipMemcpyAsync(S.d_Z.p, S.d_Xfull.p, (size_t)S.prows() * KP * 4, hipMemcpyDeviceToDevice, st));
-    else HIPCHK(hipMemcpyAsync(S.d_Z.p, S.d_X.p, (size_t)S.own_n * KP * 4, hipMemcpyDeviceToDevice, st));
-  }
-  HIPCHK(hipEventRecord(ev[3], st));
-  if (!cs_done) TRYC(column_scales(c, S, T, have_cmax));
-  const void* zhl = nullptr;
-  float wsc = 1.f, inv_sw = 1.f;
-  TRYC(presplit(c, S, T, &zhl, &wsc, &inv_sw, split_done));
-  HIPCHK(hipEventRecord(ev[4], st));
-  HIPCHK(hipMemsetAsync(c->d_err.p, 0, 4, st));
-  SolveArgs a{};
-  a.Zhl = zhl;
-  a.zero_row = S.prows();
-  a.wsc = wsc;
-  a.inv_sw = inv_sw;
-  a.Z = S.d_Z.as<float>();
-  a.ptr = T.d_ptr.as<int64_t>();
-  a.col = T.d_col.as<int32_t>();
-  a.val = T.d_val.as<float>();
-  a.lam = c->d_lam.as<float>();
-  a.X = T.d_X.as<float>();
-  a.kreal = k;
-  a.implicit = c->p.implicit_prefs;
-  a.alpha = (float)c->p.alpha;
-  a.reg = (float)c->p.reg_param;
-  a.err = c->d_err.as<int>();
-  a.colscale = c->d_cs.as<float>();
-  a.n_cu = c->n_cu;
-  const int32_t* rows = T.d_rows.as<int32_t>();
-  static const int Dof[B_HEAVY] = {16, 32, 48, 64, 96, 80};
-  // als_path_stats: light = the rows within the light limit; the tier bucket B_M80 (degree 65..80) is
-  // above it and counts with the heavy rows, whichever kernel solves it
-  T.stats[0] = T.stats[1] = T.stats[2] = T.stats[3] = 0;
-  for (int b = 0; b < B_LIGHT_END; ++b) {
-    T.stats[force_heavy ? 2 : 0] += T.boff[b + 1] - T.boff[b];
-    T.stats[force_heavy ? 3 : 1] += T.bnnz[b];
-  }
-  for (int b = B_LIGHT_END; b < NBUCKET; ++b) {
-    T.stats[2] += T.boff[b + 1] - T.boff[b];
-    T.stats[3] += T.bnnz[b];
-  }
-  // Solve chunk by chunk (one chunk unless world > 1); world > 1: each finished chunk of the new
-  // factors is gathered on the second stream while the next chunk solves.  B_M80 is
-  // launched behind the light / heavy timer event: its rows and bytes count as heavy.
-  for (int q = 0; q < T.nsolve; ++q) {
-    for (int b = 0; b < B_HEAVY; ++b) {
-      if (b == B_LIGHT_END && T.nsolve == 1) HIPCHK(hipEventRecord(ev[5], st));
-      a.rows = rows + T.cb[b][q];
-      a.desc = T.d_desc.as<int32_t>() + 4 * T.cb[b][q];
-      a.n_rows = T.cb[b][q + 1] - T.cb[b][q];
-      if (force_heavy && use_wave_kernel(c)) HIPCHK(launch_solve_wave(KP, a, st));
-      else if (force_heavy) HIPCHK(launch_solve_heavy(KP, a, st));
-      else if (b == B_L16) {  // light16.hip: degree <= 8 two rows per wave unit, then the rest
-        SolveArgs p8 = a, p16 = a;
-        p8.n_rows = T.c8[q];
-        p16.rows += T.c8[q];
-        p16.desc += 4 * T.c8[q];
-        p16.n_rows -= T.c8[q];
-        HIPCHK(launch_solve_light16(KP, p8, st, true));
-        HIPCHK(launch_solve_light16(KP, p16, st, false));
-      } else HIPCHK(launch_solve_light(KP, Dof[b], a, st));
-    }
-    TRYC(heavy_launches(c, T, a, T.cb[B_HEAVY][q], T.cb[B_HEAVY][q + 1] - T.cb[B_HEAVY][q], false, q));
-    if (multi) {
-      HIPCHK(hipEventRecord(c->evc[q], st));
-      HIPCHK(hipStreamWaitEvent(c->st2, c->evc[q], 0));
-      TRYC(gather_chunks(c, T, T.d_X.as<float>(), T.d_Xfull.as<float>(), q, q + 1, c->st2));
-    }
-  }
-  if (T.nsolve > 1) HIPCHK(hipEventRecord(ev[5], st));  // chunked: the whole solve is timed as heavy
-  if (multi) {
-    if (T.nsolve == 1) TRYC(gather_chunks(c, T, T.d_X.as<float>(), T.d_Xfull.as<float>(), 0, T.nch, c->st2));
-    HIPCHK(hipEventRecord(c->evc[8], c->st2));
-  }
-  HIPCHK(hipEventRecord(ev[6], st));
-  int err = 0, sweeps = 0;
-  HIPCHK(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, st));
-  if (c->p.implicit_prefs) HIPCHK(hipMemcpyAsync(&sweeps, eig_sweeps(c->d_eig.as<double>(), KP), 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  // Cholesky path: the device eigensolver's Jacobi sweeps (als_solver_stats), decoded like
-  // als_device_eigh (eig.hip stores -(sweeps + 1) when the budget ran out)
-  T.solver[0] = sweeps == EIG_NOT_FINITE ? 0 : (sweeps < 0 ? -sweeps - 1 : sweeps);
-  T.solver[1] = T.solver[2] = T.solver[3] = 0;
-  T.t[ALS_T_GRAM] = event_ms(ev[0], ev[1]);
-  T.t[ALS_T_EIG] = event_ms(ev[1], ev[2]);  // device eigensolver + the new basis
-  T.t[ALS_T_ROTATE] = event_ms(ev[2], ev[3]);
-  T.t[ALS_T_COMM] = event_ms(ev[3], ev[4]);
-  if (T.nsolve > 1) {
-    T.t[ALS_T_SOLVE_LIGHT] = 0.0;
-    T.t[ALS_T_SOLVE_HEAVY] = event_ms(ev[4], ev[5]);
-  } else {
-    T.t[ALS_T_SOLVE_LIGHT] = event_ms(ev[4], ev[5]);
-    T.t[ALS_T_SOLVE_HEAVY] = event_ms(ev[5], ev[6]);
-  }
-  T.t[ALS_T_HALF_TOTAL] = event_ms(ev[0], ev[6]);
-  if (sweeps == EIG_NOT_FINITE)  // eig.hip: a NaN or an Inf in the Gram (non-finite src factors, or norms past fp32)
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
-                std::string("the ") + (t == ALS_USER ? "item" : "user") +
-                    " Gram matrix is not finite (NaN or Inf in the source factors, or row norms past fp32): "
-                    "the eigensolver did not converge");
-  if (sweeps < 0)  // eig.hip: the Jacobi sweep budget ran out (the host eigensolver's "did not converge")
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE, "eigensolver did not converge (device Jacobi: " +
-                                                 std::to_string(-sweeps - 1) + " sweeps without meeting the tolerance)");
-  if (err & 3)
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
-                "LAPACK.dppsv-equivalent Cholesky met a non-positive pivot because A is not positive "
-                "definite. Is A derived from a singular matrix (e.g. collinear column values)? (flags " +
-                    std::to_string(err) + err_paths(err) + ", " + std::to_string(sweeps) + " eigensolver sweeps, " +
-                    (t == ALS_USER ? "user" : "item") + " half)" +
-                    failure_diag(c, S, T, c->p.implicit_prefs ? (multi ? S.prows() : S.own_n) : S.own_n, zhl));
-  T.has_factors = true;
-  T.orig_valid = false;
-  T.full_valid = multi;  // gathered behind the solve (st2); the next half waits for it
-  return ALS_OK;
-}
-
-}  // namespace
 
 // original-basis factors of `side`, dense order, on device: d_orig [n][KP]
 int albedo::materialize(als_ctx* c, int side) {
@@ -1006,7 +274,7 @@ int albedo::materialize(als_ctx* c, int side) {
   if (c->world == 1) {
     HIPCHK(launch_rotate(KP, S.d_X.as<float>(), c->d_P.as<float>(), S.d_orig.as<float>(), S.own_n, c->st));
   } else {  // rotate the own chunks, gather them, unpack the chunk-major layout into dense order
-    if (c->st2) HIPCHK(hipStreamWaitEvent(c->st, c->evc[8], 0));
+    if (c->st2) HIPCHK(hipStreamWaitEvent(c->st, c->evc[EVC_GATHERED], 0));
     DevBuf own, padded;
     const int64_t nown = (int64_t)S.nch * S.chpad;
     HIPCHK(own.ensure((size_t)nown * KP * 4));

@@ -1377,9 +1377,9 @@ __global__ __launch_bounds__(256) void heavy_reduce_kernel(SplitArgs s) {
 }
 
 template <int KP>
-hipError_t launch_split_kp(const SolveArgs& a, const SplitArgs& s, bool wave, hipStream_t st) {
+hipError_t launch_split_kp(const SolveArgs& a, const SplitArgs& s, hipStream_t st) {
   using R = SplitRec<KP>;
-  if (wave && KP <= 128) {
+  if constexpr (KP <= 128) {
     const hipError_t e = launch_wave_partial(KP, a, s, st);
     if (e != hipSuccess) return e;
   } else {
@@ -1393,11 +1393,11 @@ hipError_t launch_split_kp(const SolveArgs& a, const SplitArgs& s, bool wave, hi
   return hipGetLastError();
 }
 
-hipError_t launch_heavy_split(int KP, const SolveArgs& a, const SplitArgs& s, bool wave, hipStream_t st) {
+hipError_t launch_heavy_split(int KP, const SolveArgs& a, const SplitArgs& s, hipStream_t st) {
   if (s.n_chunks <= 0 || s.n_split <= 0) return hipSuccess;
-  if (KP == 64) return launch_split_kp<64>(a, s, wave, st);
-  if (KP == 128) return launch_split_kp<128>(a, s, wave, st);
-  if (KP == 256) return launch_split_kp<256>(a, s, wave, st);
+  if (KP == 64) return launch_split_kp<64>(a, s, st);
+  if (KP == 128) return launch_split_kp<128>(a, s, st);
+  if (KP == 256) return launch_split_kp<256>(a, s, st);
   return hipErrorInvalidValue;
 }
 
@@ -2120,24 +2120,17 @@ template <int KP>
 hipError_t launch_nnls_kp(const SolveArgs& a, const float* Gt, hipStream_t s) {
   const size_t lds = NnlsLds<KP>::FLOATS * 4;
   // KP >= 128: A in registers (nnls_reg_iterate); KP = 64 keeps the LDS-streamed loop
-  constexpr bool CAN_REG = KP >= 128;
-  constexpr bool reg = CAN_REG;
-  static const hipError_t attr = allow_lds(solve_nnls_kernel<KP, false>, lds);
-  static const hipError_t attr2 = allow_lds(solve_nnls_kernel<KP, true>, lds);
-  static const hipError_t attr3 = allow_lds(solve_nnls_kernel<KP, false, CAN_REG>, lds);
-  static const hipError_t attr4 = allow_lds(solve_nnls_kernel<KP, true, CAN_REG>, lds);
+  constexpr bool REG = KP >= 128;
+  static const hipError_t attr = allow_lds(solve_nnls_kernel<KP, false, REG>, lds);
+  static const hipError_t attr2 = allow_lds(solve_nnls_kernel<KP, true, REG>, lds);
   if (attr != hipSuccess) return attr;
   if (attr2 != hipSuccess) return attr2;
-  if (attr3 != hipSuccess) return attr3;
-  if (attr4 != hipSuccess) return attr4;
   // one workgroup per row, in launches of at most 2^31 work-items (an AQL dispatch's grid size is a
   // 32-bit work-item count: 4.9M rows x 1024 threads would wrap and silently drop rows)
   for (int64_t r0 = 0; r0 < a.n_rows; r0 += max_rows_per_launch(Heavy<KP>::NTH)) {
     SolveArgs b = chunk_args(a, r0, Heavy<KP>::NTH, SplitRec<KP>::FLOATS);
-    if (reg && b.prebuilt) solve_nnls_kernel<KP, true, CAN_REG><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
-    else if (reg) solve_nnls_kernel<KP, false, CAN_REG><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
-    else if (b.prebuilt) solve_nnls_kernel<KP, true><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
-    else solve_nnls_kernel<KP, false><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
+    if (b.prebuilt) solve_nnls_kernel<KP, true, REG><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
+    else solve_nnls_kernel<KP, false, REG><<<(int)b.n_rows, Heavy<KP>::NTH, lds, s>>>(b, Gt);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -2181,6 +2174,13 @@ hipError_t launch_solve_heavy(int KP, const SolveArgs& a, hipStream_t s) {
   if (KP == 128) return launch_heavy_kp<128>(a, s);
   if (KP == 256) return launch_heavy_kp<256>(a, s);
   return hipErrorInvalidValue;
+}
+
+bool explicit_reads_presplit(int KP) { return KP <= 128; }
+
+hipError_t launch_solve_explicit(int KP, const SolveArgs& a, hipStream_t s) {
+  if (a.prebuilt || KP > 128) return launch_solve_heavy(KP, a, s);
+  return launch_solve_wave(KP, a, s);
 }
 
 // =============================================================================================

@@ -1,6 +1,8 @@
-// What the host translation units share (als_engine.cpp: contexts, ingest, sweeps; topk_host.cpp:
-// top-k and NDCG; eval_host.cpp: held-out pair ranking): error reporting, the device buffer, the per-side state, the context and the few
-// engine functions the top-k host code calls.  Not part of the public C ABI (include/albedo_als.h).
+// What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
+// sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
+// held-out pair ranking): error reporting, the device buffer, the row buckets, the per-side state, the
+// context and the few functions one file calls in another.  Not part of the public C ABI
+// (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -27,6 +29,11 @@ int fail(int code, const std::string& msg);
   do {                             \
     int rc_ = (x);                 \
     if (rc_ != ALS_OK) return rc_; \
+  } while (0)
+#define NCCLCHK(x)                                                                                 \
+  do {                                                                                             \
+    ncclResult_t r_ = (x);                                                                         \
+    if (r_ != ncclSuccess) return fail(ALS_E_RCCL, std::string("RCCL error: ") + ncclGetErrorString(r_) + " in " #x); \
   } while (0)
 
 struct DevBuf {
@@ -94,12 +101,34 @@ struct Event {
   }
 };
 
-// Row buckets in list order.  B_L16 .. B_L96 hold the rows within the light limit (push-through
-// solve); B_L48 (degree 33..48) and B_M80 (degree 65..80, above the default light limit of 64) exist
-// only with the degree tiers on (als_ctx::tiers) and are empty otherwise.  B_M80 rows run the
-// push-through kernel too but count, and are timed, with the rows above the limit (B_LIGHT_END
-// splits the two groups); B_HEAVY rows take the explicit k x k path.
-enum { B_L16 = 0, B_L32 = 1, B_L48 = 2, B_L64 = 3, B_L96 = 4, B_M80 = 5, B_HEAVY = 6, NBUCKET = 7, B_LIGHT_END = B_M80 };
+// Row buckets, one table row each, in list order: the order of Side::d_rows, which fixes the launch
+// order and the layout the chunked solve indexes (Side::cb), so it is not degree order.
+//   D      the solve_light_kernel<KP, D> instance (degree <= D); 0: B_HEAVY, the explicit k x k path
+//   light  counted as light by als_path_stats and timed with ALS_T_SOLVE_LIGHT: the buckets within the
+//          light limit.  B_M80 (degree 65..80, above the default limit of 64) runs the push-through
+//          kernel too but counts, and is timed, with the rows above the limit
+//   tier   exists only with the degree tiers on (als_ctx::tiers), empty otherwise
+enum { B_L16 = 0, B_L32, B_L48, B_L64, B_L96, B_M80, B_HEAVY, NBUCKET };
+struct Bucket {
+  int D;
+  bool light, tier;
+};
+constexpr Bucket BUCKETS[NBUCKET] = {{16, true, false}, {32, true, false}, {48, true, true}, {64, true, false},
+                                     {96, true, false}, {80, false, true}, {0, false, false}};
+// the light buckets come first: B_LIGHT_END is where the light / heavy timer event goes, and the rows
+// from Side::boff[B_LIGHT_END] on are the rows above the light limit
+constexpr int light_bucket_end() {
+  int b = 0;
+  while (b < NBUCKET && BUCKETS[b].light) ++b;
+  return b;
+}
+constexpr int B_LIGHT_END = light_bucket_end();
+constexpr bool buckets_well_formed() {
+  for (int b = B_LIGHT_END; b < NBUCKET; ++b)
+    if (BUCKETS[b].light) return false;
+  return BUCKETS[B_L16].D == 16 && BUCKETS[B_HEAVY].D == 0;  // light16.hip takes B_L16, whatever the table says
+}
+static_assert(buckets_well_formed(), "light buckets first, B_L16 and B_HEAVY in their places");
 
 struct Side {
   int64_t n = 0;                 // rows (unique raw ids)
@@ -204,18 +233,30 @@ struct als_ctx {
   int split_len = 0;             // ratings per split-K chunk (0: no split)
   bool tiers = false;            // degree tiers D = 48 / D = 80 in the row layout (rank_layout)
   int slab_blocks = 0;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[8] = {};         // half-sweep stage timers (sweep_host.cpp EV_*)
   hipStream_t st2 = nullptr;     // world > 1: factor-chunk gathers behind the solve
   // als_fork: a fork views its parent's ingest buffers; the parent is freed after its last fork
   als_ctx* parent = nullptr;
   int forks = 0;
   bool doomed = false;
-  hipEvent_t evc[9] = {};        // per solve chunk: done on st; [8]: gathers done on st2
+  hipEvent_t evc[9] = {};        // per solve chunk: done on st; [EVC_GATHERED]: gathers done on st2
 };
 
 namespace albedo {
 
+// Ordering of a sharded context's two streams (world > 1), kept by sweep_host.cpp half_sweep:
+//   1. the previous half's factor gathers (st2) finish before any collective or rotation of the next
+//      half is issued: st waits on evc[EVC_GATHERED] first.  Two RCCL operations of one communicator
+//      must never overlap;
+//   2. solve chunk q's gather (st2) waits on evc[q], recorded on st behind the chunk's last solve;
+//   3. evc[EVC_GATHERED], recorded on st2 behind the last gather, closes the half's gathers; whoever
+//      reads d_Xfull or issues a collective on st (materialize) waits on it.
+constexpr int EVC_GATHERED = 8;
+
 int set_device(als_ctx* c);
+// both streams idle: before anything rewrites factor buffers with engine-stream copies, or returns to
+// the caller as "done" (world > 1: the last half's gathers run on st2 behind the solve)
+int drain(als_ctx* c);
 // Copies between the host and the context's buffers go through the engine stream c->st and complete
 // before returning (als_engine.cpp)
 hipError_t copy_st(const als_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
@@ -225,5 +266,17 @@ int materialize(als_ctx* c, int side);
 int64_t find_row(const Side& S, int32_t id);  // dense row of a raw id, -1 when unknown
 // all-gather of host blocks: buf holds world blocks of n floats (this rank's filled)
 int allgather_host(als_ctx* c, float* buf, int64_t n);
+
+// ---- sweep_host.cpp ------------------------------------------------------------------------------
+// Everything that depends on the rank / light-row limit rather than on the ratings: degree buckets,
+// split-K lists, then factor_buffers.  Called after ingest and again by als_set_params.
+int rank_layout(als_ctx* c);
+// Per-fit device state (factor buffers, Gram slabs, scratch); the factors are dropped
+int factor_buffers(als_ctx* c);
+// Gathers layout chunks [q0, q1) of the own rows `own` ([nch·chpad][KP], zero past own_n) into
+// `full` ([prows][KP]) on stream s: chunk q of every rank is one contiguous all-gather.
+int gather_chunks(als_ctx* c, const Side& S, const float* own, float* full, int q0, int q1, hipStream_t s);
+// One computeFactors call: dst side t solved from the other side's factors
+int half_sweep(als_ctx* c, int t);
 
 }  // namespace albedo

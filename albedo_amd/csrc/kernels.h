@@ -1,4 +1,5 @@
-// Internal launch interface between the host engine (als_engine.cpp) and the HIP kernels.
+// Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
+// eval_host.cpp) and the HIP kernels.
 // Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,9 +57,9 @@ struct SplitArgs {
   float* reduced;            // [n_split][split_rec_floats]
 };
 int split_rec_floats(int KP);
-// partial builds of every chunk (wave: one wave per chunk, heavy_wave.hip, KP <= 128; else one
-// 4/16-wave workgroup per chunk), then the fp64 reduction into s.reduced
-hipError_t launch_heavy_split(int KP, const SolveArgs& a, const SplitArgs& s, bool wave, hipStream_t st);
+// partial builds of every chunk (KP <= 128: one wave per chunk, heavy_wave.hip; KP = 256: one
+// 16-wave workgroup per chunk), then the fp64 reduction into s.reduced
+hipError_t launch_heavy_split(int KP, const SolveArgs& a, const SplitArgs& s, hipStream_t st);
 hipError_t launch_wave_partial(int KP, const SolveArgs& a, const SplitArgs& s, hipStream_t st);
 
 // G (fp64 [KP][KP], full symmetric) = Σ_rows Xᵀ X over rows [0, n) of X ([n][KP]).
@@ -81,6 +82,11 @@ hipError_t launch_row_desc(const int32_t* rows, int64_t n, const int64_t* ptr, i
 hipError_t launch_solve_heavy(int KP, const SolveArgs& a, hipStream_t s);
 // heavy rows, one wave per row (heavy_wave.hip), KP <= 128; rows of any degree (split rows excepted)
 hipError_t launch_solve_wave(int KP, const SolveArgs& a, hipStream_t s);
+// Rows on the explicit k x k path, whichever kernel that is: split rows (a.prebuilt) and KP = 256 take
+// launch_solve_heavy, every other row at KP <= 128 launch_solve_wave
+hipError_t launch_solve_explicit(int KP, const SolveArgs& a, hipStream_t s);
+// whether launch_solve_explicit's kernels gather the pre-split src rows (SolveArgs::Zhl) when given
+bool explicit_reads_presplit(int KP);
 
 // nonnegative = true: Spark NNLS per row; Gt = the src Gram in the NNLS tile layout (fp32).
 hipError_t launch_solve_nnls(int KP, const SolveArgs& a, const float* Gt, hipStream_t s);

@@ -45,21 +45,21 @@ def padded_rank(k):
 
 
 def light_limit(KP, light):
-    """als_engine.cpp light_limit: rows of degree <= this take the push-through (d x d) solve."""
+    """sweep_host.cpp light_limit: rows of degree <= this take the push-through (d x d) solve."""
     if light >= 0:
         return min(light, 96 if KP == 128 else 64)
     return 64 if KP >= 128 else 32
 
 
 def split_chunk(chunk=None):
-    """als_engine.cpp split_chunk_len for an ALBEDO_SPLIT_CHUNK value (None: the environment's)."""
+    """sweep_host.cpp split_chunk_len for an ALBEDO_SPLIT_CHUNK value (None: the environment's)."""
     if chunk is None:
         chunk = os.environ.get("ALBEDO_SPLIT_CHUNK")
     return max(0, int(chunk)) if chunk else DEFAULT_SPLIT_CHUNK
 
 
 def path_of(degree, KP, light, chunk):
-    """The Cholesky solve path of a row (als_engine.cpp light_limit / bucket_of / rank_layout's split
+    """The Cholesky solve path of a row (sweep_host.cpp light_limit / bucket_of / rank_layout's split
     lists); chunk is the split-K chunk length in ratings (0: no split)."""
     d = int(degree)
     if d <= light_limit(KP, light):

@@ -1,6 +1,6 @@
 """Shared pieces of the NNLS edge suite (tests/test_gpu_nnls_edges.py on the GPU, tests/test_oracle.py
 on the CPU): the NNLS degree ladder, the src-factor generators, a test-side restatement of the engine's
-NNLS path choice (als_engine.cpp rank_layout / nnls_batch_rows_limit, als_kernels.hip
+NNLS path choice (sweep_host.cpp rank_layout / nnls_batch_rows_limit, als_kernels.hip
 launch_solve_nnls), and the per-row check against the fp64 restatement of Spark's NNLS.solve.
 
 The per-row check (check_rows) asks of every dst row, with A = G + sum c y yT + lambda n I and b built in
@@ -159,7 +159,7 @@ def fit_reference(B, U0, *, max_iter, reg, alpha, implicit):
 
 def batch_limits(KP, min_slots=DEFAULT_MIN_SLOTS):
     """[(slots, degree limit)] of the lockstep variants in launch order; a closed variant (fewer slots
-    than ALBEDO_NNLS_MIN_SLOTS allows) has limit 0.  als_engine.cpp nnls_batch_rows_limit."""
+    than ALBEDO_NNLS_MIN_SLOTS allows) has limit 0.  sweep_host.cpp nnls_batch_rows_limit."""
     if min_slots not in BATCH_SLOTS:
         min_slots = DEFAULT_MIN_SLOTS
     light = LD.light_limit(KP, -1)

@@ -1,5 +1,5 @@
 """Degree tiers at padded rank 128: solve_light_kernel<128, 48> for rows of degree 33..48 and
-solve_light_kernel<128, 80> for rows of degree 65..80 (als_engine.cpp bucket_of / degree_tiers_on).
+solve_light_kernel<128, 80> for rows of degree 65..80 (sweep_host.cpp bucket_of / degree_tiers_on).
 
 Data: about 400 users x 400 items.  The first rows of either side are ladder rows whose degrees sit on
 both sides of every tier edge (31 .. 129, two rows each) plus one row each of degree 40 and 72, which in
