@@ -28,6 +28,11 @@ ALS_USER, ALS_ITEM = 0, 1
 ALS_METRIC_NDCG, ALS_METRIC_PRECISION, ALS_METRIC_MAP = 0, 1, 2
 METRICS = {"NDCG@k": ALS_METRIC_NDCG, "Precision@k": ALS_METRIC_PRECISION, "MAP": ALS_METRIC_MAP}
 ALS_T_COUNT = 8
+# als_audit.worst_path: the solve path the row layout routes a row to (ALS_PATH_* in order)
+PATH_NAMES = ["light16-pair", "light16", "light32", "light48", "light64", "light96", "tier80", "explicit", "split",
+              "nnls-lockstep", "nnls-row"]
+(ALS_PATH_LIGHT16_PAIR, ALS_PATH_LIGHT16, ALS_PATH_LIGHT32, ALS_PATH_LIGHT48, ALS_PATH_LIGHT64, ALS_PATH_LIGHT96,
+ ALS_PATH_TIER80, ALS_PATH_EXPLICIT, ALS_PATH_SPLIT, ALS_PATH_NNLS_LOCKSTEP, ALS_PATH_NNLS_ROW) = range(11)
 T_NAMES = ["gram", "eig", "rotate", "comm", "solve_light", "solve_heavy", "half_total", "_"]
 
 
@@ -44,6 +49,20 @@ class als_params(C.Structure):
         ("seed", C.c_int64),
         ("device", C.c_int32),
         ("light_max_degree", C.c_int32),
+    ]
+
+
+class als_audit(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("rows_over", C.c_int64),
+        ("non_finite", C.c_int64),
+        ("negative", C.c_int64),
+        ("worst_degree", C.c_int64),
+        ("worst_id", C.c_int32),
+        ("worst_path", C.c_int32),
+        ("worst_eta", C.c_double),
+        ("sum_eta", C.c_double),
     ]
 
 
@@ -113,6 +132,7 @@ SIGNATURES = [
     ("als_last_timings", C.c_int, [P, C.c_int, F64P, C.c_int]),
     ("als_path_stats", C.c_int, [P, C.c_int, I64P]),
     ("als_solver_stats", C.c_int, [P, C.c_int, I64P]),
+    ("als_audit_rows", C.c_int, [P, C.c_int, C.c_double, F64P, C.POINTER(als_audit)]),
     ("als_topk_stats", C.c_int, [P, I64P]),
     ("als_topk_timing", C.c_int, [P, F64P]),
     ("als_get_basis", C.c_int, [P, C.c_int, F64P]),

@@ -526,6 +526,21 @@ class ALSModel(_Params):
         check(load().als_eval_pairs_timing(self._h, ptr(out, C.c_double)))
         return dict(zip(("map", "sort", "score", "select", "metric"), out.tolist()))
 
+    def audit(self, side, tol, per_row=False):
+        """als_audit_rows: every row of `side` against its normal equation, in fp64 on the device.
+
+        Returns the summary as a dict (rows, rows_over, non_finite, negative, worst_id, worst_degree,
+        worst_path as a name of _lib.PATH_NAMES, worst_eta, sum_eta) and, with per_row, the relative
+        residual of every row in ascending id order.  Needs the ratings: a model of ALS.fit(dataset) has
+        them, a loaded model or one of a ParamMap list does not (IllegalStateException)."""
+        lib = load()
+        a = _lib.als_audit()
+        eta = np.empty(max(int(lib.als_num_rows(self._h, int(side))), 0), np.float64) if per_row else None
+        check(lib.als_audit_rows(self._h, int(side), float(tol), ptr(eta, C.c_double) if per_row else None, C.byref(a)))
+        out = {name: getattr(a, name) for name, _ in _lib.als_audit._fields_}
+        out["worst_path"] = _lib.PATH_NAMES[a.worst_path] if a.worst_path >= 0 else None
+        return (out, eta) if per_row else out
+
     # ---- persistence (Spark 2.2 ALSModelWriter / ALSModelReader layout: albedo_amd/persistence.py) ----
     MODEL_PARAMS = ("userCol", "itemCol", "predictionCol", "coldStartStrategy")  # ALSModelParams
 

@@ -262,25 +262,35 @@ float albedo::event_ms(hipEvent_t a, hipEvent_t b) {
   return ms;
 }
 
+int albedo::original_rows(als_ctx* c, int side, DevBuf* own, DevBuf* padded) {
+  Side& S = c->s[side];
+  if (!S.has_factors) return fail(ALS_E_STATE, "factors are not available (call fit first)");
+  const int KP = c->KP;
+  HIPCHK(c->d_P.ensure((size_t)KP * KP * 4));
+  HIPCHK(launch_basis_t32(S.d_B.as<double>(), c->d_P.as<float>(), KP, c->st));
+  if (c->st2) HIPCHK(hipStreamWaitEvent(c->st, c->evc[EVC_GATHERED], 0));
+  const int64_t nown = (int64_t)S.nch * S.chpad;
+  HIPCHK(own->ensure((size_t)nown * KP * 4));
+  HIPCHK(launch_rotate(KP, S.d_X.as<float>(), c->d_P.as<float>(), own->as<float>(), nown, c->st));
+  if (!padded) return ALS_OK;
+  HIPCHK(padded->ensure((size_t)std::max<int64_t>(S.prows(), 1) * KP * 4));
+  return gather_chunks(c, S, own->as<float>(), padded->as<float>(), 0, S.nch, c->st);
+}
+
 // original-basis factors of `side`, dense order, on device: d_orig [n][KP]
 int albedo::materialize(als_ctx* c, int side) {
   Side& S = c->s[side];
   if (S.orig_valid) return ALS_OK;
   if (!S.has_factors) return fail(ALS_E_STATE, "factors are not available (call fit first)");
   const int KP = c->KP;
-  HIPCHK(c->d_P.ensure((size_t)KP * KP * 4));
-  HIPCHK(launch_basis_t32(S.d_B.as<double>(), c->d_P.as<float>(), KP, c->st));
   HIPCHK(S.d_orig.ensure((size_t)std::max<int64_t>(S.n, 1) * KP * 4));
   if (c->world == 1) {
+    HIPCHK(c->d_P.ensure((size_t)KP * KP * 4));
+    HIPCHK(launch_basis_t32(S.d_B.as<double>(), c->d_P.as<float>(), KP, c->st));
     HIPCHK(launch_rotate(KP, S.d_X.as<float>(), c->d_P.as<float>(), S.d_orig.as<float>(), S.own_n, c->st));
   } else {  // rotate the own chunks, gather them, unpack the chunk-major layout into dense order
-    if (c->st2) HIPCHK(hipStreamWaitEvent(c->st, c->evc[EVC_GATHERED], 0));
     DevBuf own, padded;
-    const int64_t nown = (int64_t)S.nch * S.chpad;
-    HIPCHK(own.ensure((size_t)nown * KP * 4));
-    HIPCHK(padded.ensure((size_t)std::max<int64_t>(S.prows(), 1) * KP * 4));
-    HIPCHK(launch_rotate(KP, S.d_X.as<float>(), c->d_P.as<float>(), own.as<float>(), nown, c->st));
-    TRYC(gather_chunks(c, S, own.as<float>(), padded.as<float>(), 0, S.nch, c->st));
+    TRYC(original_rows(c, side, &own, &padded));
     for (int r = 0; r < c->world; ++r) {
       const int64_t nr = S.starts[r + 1] - S.starts[r];
       for (int q = 0; q < S.nch && (int64_t)q * S.chpad < nr; ++q) {

@@ -1,6 +1,6 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking): error reporting, the device buffer, the row buckets, the per-side state, the
+// held-out pair ranking; audit_host.cpp: the row audit): error reporting, the device buffer, the row buckets, the per-side state, the
 // context and the few functions one file calls in another.  Not part of the public C ABI
 // (include/albedo_als.h).
 #pragma once
@@ -263,6 +263,10 @@ hipError_t copy_st(const als_ctx* c, void* dst, const void* src, size_t bytes, h
 float event_ms(hipEvent_t a, hipEvent_t b);
 // original-basis factors of `side`, dense order, on device: d_orig [n][KP]
 int materialize(als_ctx* c, int side);
+// world > 1, the first half of materialize: this rank's rows of `side` rotated into the original basis
+// (own: [nch·chpad][KP], zero past own_n) and, when `padded` is given, every rank's rows gathered into
+// the padded layout ([prows][KP], what the other side's CSR col indexes).  Queued on c->st.
+int original_rows(als_ctx* c, int side, DevBuf* own, DevBuf* padded);
 int64_t find_row(const Side& S, int32_t id);  // dense row of a raw id, -1 when unknown
 // all-gather of host blocks: buf holds world blocks of n floats (this rank's filled)
 int allgather_host(als_ctx* c, float* buf, int64_t n);
@@ -271,6 +275,10 @@ int allgather_host(als_ctx* c, float* buf, int64_t n);
 // Everything that depends on the rank / light-row limit rather than on the ratings: degree buckets,
 // split-K lists, then factor_buffers.  Called after ingest and again by als_set_params.
 int rank_layout(als_ctx* c);
+// The solve path (ALS_PATH_*) that layout gives own row r of side T (als_audit_rows' worst_path)
+int row_path(const als_ctx* c, const Side& T, int64_t r);
+// Sum of c->d_G ([KP][KP] fp64) over the ranks, on c->st (nothing to do when world = 1)
+int allreduce_G(als_ctx* c);
 // Per-fit device state (factor buffers, Gram slabs, scratch); the factors are dropped
 int factor_buffers(als_ctx* c);
 // Gathers layout chunks [q0, q1) of the own rows `own` ([nch·chpad][KP], zero past own_n) into

@@ -1,5 +1,5 @@
 // Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
-// eval_host.cpp) and the HIP kernels.
+// eval_host.cpp, audit_host.cpp) and the HIP kernels.
 // Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -285,6 +285,47 @@ hipError_t eval_metric(int metric, const int32_t* pred, int pred_width, const in
                        int64_t n_users, int k, const double* gain, double* out, hipStream_t s);
 // *out = bits of max_r ||T[r][0..kreal)||_2 computed in fp64
 hipError_t launch_rownorm_max(const float* T, int64_t n, int KP, int kreal, unsigned long long* out, hipStream_t s);
+
+// ---- row audit (audit.hip): the fp64 normal-equation residual of every dst row (als_audit_rows) -------
+struct AuditArgs {
+  const float* Y;            // src factors in the original basis, [*][KP], indexed by col
+  const float* X;            // dst rows in the original basis, [n rows][KP] (local row index, like ptr)
+  const int64_t* ptr;        // dst CSR of the own rows
+  const int32_t* col;
+  const float* val;
+  const double* G;           // fp64 src Gram [KP][KP] (implicit), null when explicit
+  double* GX;                // scratch [nb][KP]: G·x of the batch's rows; null when explicit
+  int64_t row0, nb;          // the batch: rows [row0, row0 + nb)
+  int implicit, nonneg;
+  double alpha, reg;
+  double gnorm;              // ‖G‖_F (0 when explicit)
+  int64_t chunk;             // rows of more ratings are cut into chunks of this many
+  const int32_t* chunk_row;  // [n_chunks] dst row of each chunk, rows ascending, a row's chunks in order
+  const int32_t* chunk_idx;  // [n_chunks] chunk number within its row
+  int64_t n_chunks;
+  const int32_t* long_row;   // [n_long] the rows above `chunk`, ascending
+  const int64_t* long_slot0; // [n_long + 1] first chunk of each
+  double* partial;           // [n_chunks][2·KP + 2] chunk records: Σ c (y·x) y, Σ w y, Σ c ‖y‖², n
+  double* eta;               // out [n rows]
+  int32_t* neg;              // out [n rows]: nonneg and a component of x below zero
+};
+struct AuditSummary {
+  long long over, non_finite, negative;
+  long long worst_row;       // -1: no rows
+  double worst_eta, sum;
+};
+constexpr int AUDIT_SUM_BLOCKS = 1024;  // records of launch_audit_summary's first pass (`part`)
+// G = Σ x xᵀ over rows [0, n) of X in fp64 throughout; slab: nblk·KP·KP doubles, nblk = audit_gram_blocks(n)
+int audit_gram_blocks(int64_t n);
+hipError_t launch_audit_gram(int KP, const float* X, int64_t n, double* slab, int nblk, double* G, hipStream_t s);
+// the partial records of every chunk of the long rows (once per call, before the batches)
+hipError_t launch_audit_chunks(int KP, const AuditArgs& g, hipStream_t s);
+// one batch: G·x, the rows of at most `chunk` ratings, then the long rows [l0, l0 + n_long) of the list,
+// which are the batch's
+hipError_t launch_audit_rows(int KP, const AuditArgs& g, int64_t l0, int64_t n_long, hipStream_t s);
+// rows with !(eta <= tol), non-finite and negative counts, the worst row and Σ eta, added in a fixed order
+hipError_t launch_audit_summary(const double* eta, const int32_t* neg, int64_t n, double tol, AuditSummary* part,
+                                AuditSummary* out, hipStream_t s);
 
 // Ingest (ingest.hip): COO -> remap + CSR.
 struct DeviceBuf;

@@ -216,6 +216,28 @@ int albedo::rank_layout(als_ctx* c) {
   return factor_buffers(c);
 }
 
+// The ALS_PATH_* of own row r of side T: what bucket_rows, group_by_chunk and split_lists above make of
+// its degree.  nonnegative: the lockstep kernel takes the light list's rows up to the largest degree
+// limit of its variants (the list is degree-ascending), the per-row kernel every other row, split-K
+// rows included.  The layout's routing only: a half that forced the explicit path is not reflected.
+int albedo::row_path(const als_ctx* c, const Side& T, int64_t r) {
+  const int64_t d = T.h_deg[r];
+  if (c->p.nonnegative) {
+    int64_t lim = 0;
+    for (int v = 0; v < 5; ++v) lim = std::max(lim, nnls_batch_rows_limit(c, v));
+    return d <= lim ? ALS_PATH_NNLS_LOCKSTEP : ALS_PATH_NNLS_ROW;
+  }
+  switch (bucket_of(d, light_limit(c), c->tiers)) {
+    case B_L16: return d <= 8 ? ALS_PATH_LIGHT16_PAIR : ALS_PATH_LIGHT16;
+    case B_L32: return ALS_PATH_LIGHT32;
+    case B_L48: return ALS_PATH_LIGHT48;
+    case B_L64: return ALS_PATH_LIGHT64;
+    case B_L96: return ALS_PATH_LIGHT96;
+    case B_M80: return ALS_PATH_TIER80;
+    default: return c->split_len > 0 && d > c->split_len ? ALS_PATH_SPLIT : ALS_PATH_EXPLICIT;
+  }
+}
+
 // Per-fit device state: split-K records, factor / rotated-factor buffers, Gram slabs and scratch;
 // the factors are dropped (the next fit initialises them).
 int albedo::factor_buffers(als_ctx* c) {
@@ -264,9 +286,7 @@ int albedo::factor_buffers(als_ctx* c) {
 }
 
 // ---- collectives ------------------------------------------------------------------------------
-namespace {
-
-int allreduce_G(als_ctx* c) {
+int albedo::allreduce_G(als_ctx* c) {
   const int64_t n = (int64_t)c->KP * c->KP;
   if (c->world == 1) return ALS_OK;
   if (c->comm) {
@@ -281,6 +301,8 @@ int allreduce_G(als_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->st));
   return ALS_OK;
 }
+
+namespace {
 
 // in-place all-gather on stream s: rank r's rows_per_rank rows at buf + r·rows_per_rank·KP
 int allgather_rows(als_ctx* c, float* buf, int64_t rows_per_rank, hipStream_t s) {

@@ -233,6 +233,44 @@ int als_path_stats(const als_ctx* ctx, int dst_side, int64_t* out4);
  *   Gram (0 without implicitPrefs), out[1..3] = 0.  A half-sweep whose eigensolver spends its sweep
  *   budget without converging fails with ALS_E_NOT_POSITIVE_DEFINITE. */
 int als_solver_stats(const als_ctx* ctx, int dst_side, int64_t* out4);
+/* The solve path the context's row layout routes a row to (als_audit.worst_path).  It is the layout's
+ * routing (degree, light limit, degree tiers, split-K chunk; nonnegative: lockstep or per-row NNLS kernel,
+ * split-K rows counting with the per-row kernel): a half-sweep that sent every row to the explicit path
+ * (regParam = 0) is not reflected. */
+enum { ALS_PATH_LIGHT16_PAIR = 0, ALS_PATH_LIGHT16, ALS_PATH_LIGHT32, ALS_PATH_LIGHT48, ALS_PATH_LIGHT64,
+       ALS_PATH_LIGHT96, ALS_PATH_TIER80, ALS_PATH_EXPLICIT, ALS_PATH_SPLIT, ALS_PATH_NNLS_LOCKSTEP,
+       ALS_PATH_NNLS_ROW };
+typedef struct als_audit {
+  int64_t rows;         /* own dst rows audited */
+  int64_t rows_over;    /* rows with !(eta <= tol): a non-finite eta counts */
+  int64_t non_finite;   /* rows whose eta is NaN/Inf */
+  int64_t negative;     /* nonnegative = true: rows with a component < 0 (else 0) */
+  int64_t worst_degree;
+  int32_t worst_id;     /* raw id of the row with the largest eta (non-finite ranks above all; ties: lowest id) */
+  int32_t worst_path;   /* ALS_PATH_*: the path this context's layout routes that row to */
+  double  worst_eta, sum_eta;
+} als_audit;
+/* Every own row of dst_side checked against its normal equation, in fp64 on the device, from the current
+ * factors of both sides in the original basis (what als_get_factors returns).  With G the fp64 Gram of
+ * all src rows (implicitPrefs; 0 otherwise), and per rating c = alpha·|r|, w = (r > 0 ? 1 + c : 0),
+ * n = the count of r > 0 (implicitPrefs) or c = 1, w = r, n = the degree:
+ *   r_j = G·x_j + sum_i c_i (y_i·x_j) y_i + regParam·n_j·x_j - sum_i w_i y_i
+ *   eta_j = |r_j|_2 / ((|G|_F + sum_i c_i |y_i|^2 + regParam·n_j)·|x_j|_2 + |sum_i w_i y_i|_2), 0 when
+ * the denominator is 0.  nonnegative = true: r is the KKT residual (component m is r_m where x_m > 0,
+ * else min(r_m, 0)).  One pass over the ratings, O(nnz·rank); nothing a half-sweep computed is used, so
+ * the call is stateless: right after als_half_sweep(t) the audit of t is the solve's backward error, on
+ * the other side it measures the distance from that side's fixed point, and it works on injected factors
+ * with no sweep at all.  eta_out (or NULL): [als_num_rows] in ascending id order like als_get_degrees,
+ * NaN for rows other ranks own; *out summarises the own rows (worst_id = -1, worst_path = -1 when there
+ * are none).  world > 1: collective (one Gram all-reduce, one factor gather), every rank calls it and
+ * receives the summary of its own rows.  Forks may call it.  ALS_E_STATE without ratings (model-only
+ * contexts) or when a side has no factors; ALS_E_INVALID_ARGUMENT for a bad side, a NaN tol, a null out.
+ * tol: the engine's solves measure at most 1.2e-7 on the degree ladder of the test suite (the
+ * row audit), so 16 times that, 2e-6, is the recommended working tolerance; 1e-4·sqrt(rank) is the
+ * guaranteed bound.  Rows longer than ALBEDO_AUDIT_CHUNK ratings (environment; default: a quarter of
+ * one wave's share of the ratings, at least 512) are summed in chunks, in chunk order. */
+int als_audit_rows(als_ctx* ctx, int dst_side, double tol, double* eta_out /* [als_num_rows] or NULL */,
+                   als_audit* out);
 /* Top-k counters since als_create (als_recommend with k <= 64): out[0] = src rows through the MFMA
  * scan, out[1] = rows whose candidate set failed certification and were re-scored by the exact scan,
  * out[2] = dst rows the scan waves scored (a wave skips a chunk none of its rows can use), out[3] = the same without the chunk
