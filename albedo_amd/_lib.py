@@ -66,6 +66,15 @@ class als_audit(C.Structure):
     ]
 
 
+class als_fold_params(C.Structure):
+    _fields_ = [
+        ("reg_param", C.c_double),
+        ("alpha", C.c_double),
+        ("implicit_prefs", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class ALSError(RuntimeError):
     """Base class; `code` is the ALS_E_* value."""
 
@@ -121,6 +130,9 @@ SIGNATURES = [
     ("als_model_create", C.c_int, [C.c_int32, C.c_int64, I32P, F32P, C.c_int64, I32P, F32P, C.c_int32, C.POINTER(P)]),
     ("als_recommend", C.c_int, [P, C.c_int, C.c_int32, I32P, C.c_int64, I32P, I32P, F32P]),
     ("als_predict", C.c_int, [P, C.c_int64, I32P, I32P, F32P]),
+    ("als_fold_in", C.c_int, [P, C.c_int, C.POINTER(als_fold_params), C.c_int64, I32P, I32P, F32P, C.c_int64, I64P, I32P,
+                              I64P, F32P]),
+    ("als_fold_in_timing", C.c_int, [P, F64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
     ("als_evaluate_ranking", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P,
                                        C.c_int64]),
@@ -190,3 +202,42 @@ def device_count() -> int:
     check(load().als_device_count(C.byref(n)))
     return n.value
 
+
+
+def fold_in(ctx, side, row_id, src_id, rating, rank, reg_param=None, alpha=None, implicit_prefs=None, cap=None):
+    """als_fold_in on the context handle `ctx`: (ids ascending, degrees, factors [n_rows][rank]) of the distinct
+    row ids.  The three parameters go together: all None means the context's own (fp = NULL).  cap: an upper
+    bound of the number of distinct row ids the caller knows (default: they are counted here)."""
+    import numpy as np
+
+    row_id = np.ascontiguousarray(row_id, dtype=np.int32)
+    src_id = np.ascontiguousarray(src_id, dtype=np.int32)
+    rating = np.ascontiguousarray(rating, dtype=np.float32)
+    n = int(row_id.shape[0])
+    if src_id.shape != (n,) or rating.shape != (n,):
+        raise ValueError("row_id, src_id and rating should be one-dimensional and of one length")
+    given = [v is not None for v in (reg_param, alpha, implicit_prefs)]
+    fp = None
+    if any(given):
+        if not all(given):
+            raise ValueError("reg_param, alpha and implicit_prefs are given together or not at all")
+        fp = C.byref(als_fold_params(float(reg_param), float(alpha), int(bool(implicit_prefs)), 0))
+    cap = int(np.unique(row_id).size) if cap is None else int(cap)
+    ids = np.empty(cap, dtype=np.int32)
+    deg = np.empty(cap, dtype=np.int64)
+    fac = np.empty((cap, rank), dtype=np.float32)
+    nr = C.c_int64(0)
+    check(load().als_fold_in(ctx, side, fp, n, ptr(row_id, C.c_int32), ptr(src_id, C.c_int32), ptr(rating, C.c_float),
+                             cap, C.byref(nr), ptr(ids, C.c_int32), ptr(deg, C.c_int64), ptr(fac, C.c_float)))
+    if nr.value > cap:
+        raise ValueError(f"fold_in: {nr.value} distinct row ids, cap {cap}")
+    return ids[:nr.value].copy(), deg[:nr.value].copy(), fac[:nr.value].copy()
+
+
+def fold_in_timing(ctx):
+    """als_fold_in_timing: device ms of the last call: [map + sort + CSR, src Gram, solve, total]."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.float64)
+    check(load().als_fold_in_timing(ctx, ptr(out, C.c_double)))
+    return out

@@ -303,6 +303,7 @@ class ALSModel(_Params):
         self._p.update(params)
         self._h = handle
         self._cache = {}
+        self._loaded = False  # ALSModel.load: the estimator's params are not known
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -541,6 +542,72 @@ class ALSModel(_Params):
         out["worst_path"] = _lib.PATH_NAMES[a.worst_path] if a.worst_path >= 0 else None
         return (out, eta) if per_row else out
 
+    # ---- fold-in: factors for rows the fit did not see (als_fold_in) ---------------------------------
+    def _fold_params(self, regParam, alpha, implicitPrefs):
+        vals = dict(regParam=regParam, alpha=alpha, implicitPrefs=implicitPrefs)
+        for k, v in vals.items():
+            if v is None:
+                if self._loaded:  # Spark's saved ALSModel carries the rank and the column names only
+                    raise ValueError(f"foldIn on a loaded ALSModel needs {k}: the saved model does not carry it")
+                vals[k] = self._p[k]
+        return float(vals["regParam"]), float(vals["alpha"]), bool(vals["implicitPrefs"])
+
+    @staticmethod
+    def _side(side):
+        if side in ("user", _lib.ALS_USER):
+            return _lib.ALS_USER
+        if side in ("item", _lib.ALS_ITEM):
+            return _lib.ALS_ITEM
+        raise ValueError(f"side should be 'user' or 'item', not {side!r}")
+
+    def fold_in_np(self, rows, srcs, ratings, side="user", regParam=None, alpha=None, implicitPrefs=None):
+        """(ids ascending, degrees, factors [n, rank]) of the distinct ids of `rows`, each solved from its
+        (row, src, rating) triples against the model's frozen factors of the other side (als_fold_in).
+        Triples with a src id the model does not know are dropped; a row left with none gets zeros."""
+        t = self._side(side)
+        cols = (self._p["userCol"], self._p["itemCol"])
+        reg, al, imp = self._fold_params(regParam, alpha, implicitPrefs)
+        r = np.ascontiguousarray(_checked_cast(rows, cols[t]))
+        s = np.ascontiguousarray(_checked_cast(srcs, cols[1 - t]))
+        return _lib.fold_in(self._h, t, r, s, np.ascontiguousarray(ratings, dtype=np.float32), self.rank, reg, al, imp)
+
+    def foldIn(self, dataset, side="user", regParam=None, alpha=None, implicitPrefs=None):
+        """Factors of new users (side="user") or items from their ratings, as a frame of (id, features)
+        shaped like userFactors.  A model of ALS.fit defaults regParam, alpha and implicitPrefs to its own;
+        a loaded model needs all three."""
+        t = self._side(side)
+        self._fold_params(regParam, alpha, implicitPrefs)  # a missing parameter is named before a missing column
+        cols = (self._p["userCol"], self._p["itemCol"])
+        ids, _, f = self.fold_in_np(_column(dataset, cols[t]), _column(dataset, cols[1 - t]),
+                                    _column(dataset, self._p["ratingCol"]), t, regParam, alpha, implicitPrefs)
+        return self._frame(ids, f)
+
+    def recommendForNewUsers(self, dataset, numItems, **fold_kw):
+        """recommendForUserSubset for users the model has not seen: their factors are folded in from
+        `dataset` (foldIn's keywords apply), then scored against the model's items."""
+        lib = load()
+        self._fold_params(*(fold_kw.get(k) for k in ("regParam", "alpha", "implicitPrefs")))
+        ids, _, f = self.fold_in_np(_column(dataset, self._p["userCol"]), _column(dataset, self._p["itemCol"]),
+                                    _column(dataset, self._p["ratingCol"]), _lib.ALS_USER, **fold_kw)
+        ii, itf = self.item_factors_np()
+        ii, itf = np.ascontiguousarray(ii), np.ascontiguousarray(itf)
+        h = C.c_void_p()
+        check(lib.als_model_create(self.rank, ids.size, ptr(ids, C.c_int32), ptr(f, C.c_float), ii.size,
+                                   ptr(ii, C.c_int32), ptr(itf, C.c_float), int(self._p["device"]), C.byref(h)))
+        try:
+            src = np.empty(ids.size, dtype=np.int32)
+            dst = np.empty((ids.size, numItems), dtype=np.int32)
+            sc = np.empty((ids.size, numItems), dtype=np.float32)
+            check(lib.als_recommend(h, _lib.ALS_USER, int(numItems), None, ids.size, ptr(src, C.c_int32),
+                                    ptr(dst, C.c_int32), ptr(sc, C.c_float)))
+        finally:
+            lib.als_destroy(h)
+        return self._rec_frame(src, dst, sc, self._p["userCol"], self._p["itemCol"])
+
+    def fold_in_timing(self):
+        """Device ms of the last fold-in: csr (map + sort + CSR), gram (0 when cached), solve, total."""
+        return dict(zip(("csr", "gram", "solve", "total"), _lib.fold_in_timing(self._h).tolist()))
+
     # ---- persistence (Spark 2.2 ALSModelWriter / ALSModelReader layout: albedo_amd/persistence.py) ----
     MODEL_PARAMS = ("userCol", "itemCol", "predictionCol", "coldStartStrategy")  # ALSModelParams
 
@@ -576,4 +643,5 @@ class ALSModel(_Params):
         params.update({k: v for k, v in meta.get("paramMap", {}).items() if k in _Params._defaults})
         params["rank"] = rank
         model = cls(h, params, uid=meta.get("uid"))
+        model._loaded = True
         return model

@@ -233,6 +233,7 @@ int upload_factors(als_ctx* c, int side, const float* f, int64_t ld) {
   HIPCHK(launch_identity(S.d_B.as<double>(), c->KP, c->st));
   S.has_factors = true;
   S.orig_valid = false;
+  S.fold_gram_valid = false;
   S.full_valid = false;
   return ALS_OK;
 }
@@ -622,6 +623,7 @@ int als_init_factors_random(als_ctx* c, uint64_t seed) {
     HIPCHK(launch_identity(S.d_B.as<double>(), c->KP, c->st));
     S.has_factors = true;
     S.orig_valid = false;
+    S.fold_gram_valid = false;
     S.full_valid = false;
   }
   HIPCHK(hipStreamSynchronize(c->st));
@@ -753,6 +755,7 @@ int als_model_create(int32_t rank, int64_t nu, const int32_t* uids, const float*
       return fail(ALS_E_OUT_OF_MEMORY, "failed to upload factors");
     }
     S.orig_valid = true;
+    S.fold_gram_valid = false;
     S.has_factors = true;
     S.starts = {0, S.n};
     S.maxrows = S.n;

@@ -1,6 +1,6 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking; audit_host.cpp: the row audit): error reporting, the device buffer, the row buckets, the per-side state, the
+// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in): error reporting, the device buffer, the row buckets, the per-side state, the
 // context and the few functions one file calls in another.  Not part of the public C ABI
 // (include/albedo_als.h).
 #pragma once
@@ -167,6 +167,8 @@ struct Side {
   int64_t solver[4] = {0};       // NNLS iterations: sum over rows, max, rows (last half-sweep)
   DevBuf d_orig;                 // [n][KP] original-basis factors, dense order (materialised)
   bool orig_valid = false;
+  DevBuf d_foldG;                // fp64 [KP][KP] Gram of d_orig, formed and used by als_fold_in alone
+  bool fold_gram_valid = false;  // d_foldG is the Gram of the current factors (cleared with orig_valid)
   // split-K of the heavy tail: the first n_split heavy rows (degree > split chunk), their chunks
   int64_t n_split = 0, n_chunks = 0;
   DevBuf d_chunk_row, d_chunk_idx, d_slot0;
@@ -218,6 +220,8 @@ struct als_ctx {
   double topk_ms[5] = {0, 0, 0, 0, 0};
   // device time of the last pair-ranking call (ms): map, sort, score, select, metric (als_eval_pairs_timing)
   double eval_ms[5] = {0, 0, 0, 0, 0};
+  // device time of the last als_fold_in call (ms): map + sort + CSR, src Gram, solve, total
+  double fold_ms[4] = {0, 0, 0, 0};
   hipEvent_t evt[5] = {};
   // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
   // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was

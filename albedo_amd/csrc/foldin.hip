@@ -1,0 +1,349 @@
+// als_fold_in: the factors of rows that were not in the fit, each solved against the frozen factors of
+// the other side (include/albedo_als.h).  For row j with ratings r_i of src rows y_i
+//   (G + Σ_i c_i y_i y_iᵀ + λ n I) x = Σ_i w_i y_i
+// with G, c, w and n as the row audit (audit.hip) defines them: Spark's computeFactors for one row.
+//
+// Written like audit.hip and for the same reason: it must not disturb, or depend on, the solve kernels
+// of the half-sweep.  Plain HIP, no inline asm, no MFMA, none of device_common.h; the factors are in the
+// original basis and everything is fp64 from the first product on.  The system has the model rank k,
+// not the padded one.
+//
+//   fold_key_kernel .. fold_rows_kernel   the triples as a CSR: src ids to rows by binary search, one
+//                      64-bit radix sort on (row id, src row), run lengths, degrees, rows by descending degree
+//   fold_solve_kernel  one workgroup per row, persistent over the degree-ordered list.
+//     build   FOLD_TILE src rows at a time are gathered into LDS as fp32 (every load of a tile is issued
+//             before the first is stored).  The threads form a TS x TS grid; thread (ty, tx) owns the
+//             entries (i, m) with i = ty mod TS, m = tx mod TS of the lower triangle, 36 doubles at
+//             KP = 64 (TS = 8, one wave), KP = 128 (TS = 16) and KP = 256 (TS = 32), and adds c·y_i·y_m
+//             rating by rating in CSR order: no atomics, no split, one fixed order of addition.
+//     factor  right-looking Cholesky, column by column, on the sums where they are: the column goes through
+//             LDS, every thread scales the entries it needs and updates its own part of the trailing
+//             triangle in registers.  The finished columns of L are left in the packed lower triangle
+//             (row-major), which takes the place of the tile in LDS at KP <= 128 (66 KB at 128: two rows
+//             per CU); at KP = 256 it is 263 KB and lives in the workgroup's slab of global scratch, written
+//             once per column.  L z = b rides along with the columns; the back substitution reads the
+//             triangle, one column per step.
+//     A pivot <= 0 or NaN ends the row and leaves its index in *bad (integer atomicMin).
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+
+#include "kernels.h"
+
+namespace albedo {
+
+namespace {
+
+constexpr uint32_t FOLD_DROPPED = 0xFFFFFFFFu;
+
+inline int fold_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
+
+__global__ void fold_key_kernel(const int32_t* __restrict__ row_id, const int32_t* __restrict__ src_id, int64_t n,
+                                const int32_t* __restrict__ ids, int64_t n_ids, uint64_t* __restrict__ key) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t v = src_id[i];
+    int64_t lo = 0, hi = n_ids;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (ids[mid] < v) lo = mid + 1;
+      else hi = mid;
+    }
+    const uint32_t c = (lo < n_ids && ids[lo] == v) ? (uint32_t)lo : FOLD_DROPPED;
+    key[i] = ((uint64_t)((uint32_t)row_id[i] ^ 0x80000000u) << 32) | c;
+  }
+}
+
+__global__ void fold_split_kernel(const uint64_t* __restrict__ key, int64_t n, uint32_t* __restrict__ hi,
+                                  uint32_t* __restrict__ col) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    hi[i] = (uint32_t)(key[i] >> 32);
+    col[i] = (uint32_t)key[i];
+  }
+}
+
+// per row: its raw id and the count of its live triples (the dropped ones end its range)
+__global__ void fold_rows_kernel(const uint32_t* __restrict__ runs, const int64_t* __restrict__ ptr,
+                                 const uint32_t* __restrict__ col, int64_t n_rows, int32_t* __restrict__ ids,
+                                 uint32_t* __restrict__ deg) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * blockDim.x) {
+    int64_t lo = ptr[r], hi = ptr[r + 1];
+    const int64_t p0 = lo;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (col[mid] != FOLD_DROPPED) lo = mid + 1;
+      else hi = mid;
+    }
+    deg[r] = (uint32_t)(lo - p0);
+    ids[r] = (int32_t)(runs[r] ^ 0x80000000u);
+  }
+}
+
+__global__ void fold_iota_kernel(int32_t* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (int32_t)i;
+}
+
+// ---- the solve -------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int fold_tri(int KP) { return KP * (KP + 1) / 2; }
+// the triangle shares its LDS with the gather tile: the build holds its sums in registers until the last
+// tile has been read
+__host__ __device__ constexpr size_t fold_front_bytes(int KP, bool tri_lds) {
+  const size_t tile = (size_t)FOLD_TILE * KP * 4, tri = tri_lds ? (size_t)fold_tri(KP) * 8 : 0;
+  return tile > tri ? tile : tri;
+}
+// + the right-hand side / solution, two column buffers, z, 1 / diag(L), and c, w and (r > 0) of the tile's ratings
+__host__ __device__ constexpr size_t fold_lds_bytes(int KP, bool tri_lds) {
+  return fold_front_bytes(KP, tri_lds) + (size_t)(5 * KP + 3 * FOLD_TILE) * 8;
+}
+
+__device__ inline int tri_at(int i, int m) { return i * (i + 1) / 2 + m; }  // m <= i
+
+template <int KP, int TS, bool TRI_LDS>
+__global__ __launch_bounds__(TS* TS) void fold_solve_kernel(const FoldArgs a) {
+  constexpr int NT = TS * TS, NB = KP / TS, Q = KP / 4;
+  constexpr int PER = FOLD_TILE * Q / NT;  // 16-byte loads per thread and tile
+  static_assert(FOLD_TILE * Q % NT == 0 && KP <= NT && FOLD_TILE <= NT, "tile and thread grid do not match");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* tile = reinterpret_cast<float*>(smem);  // [FOLD_TILE][KP]
+  double* vec = reinterpret_cast<double*>(smem + fold_front_bytes(KP, TRI_LDS));  // b, then x
+  double* colb = vec + KP;                                                        // two column buffers
+  double* zb = colb + 2 * KP;
+  double* dinv = zb + KP;
+  double* cw = dinv + KP;
+  double* ww = cw + FOLD_TILE;
+  double* pw = ww + FOLD_TILE;
+  double* A = TRI_LDS ? reinterpret_cast<double*>(smem) : a.scratch + (size_t)blockIdx.x * fold_tri(KP);
+  const int tid = threadIdx.x, tx = tid % TS, ty = tid / TS;
+  const int k = a.k;
+  for (int64_t li = blockIdx.x; li < a.n_rows; li += gridDim.x) {
+    const int64_t row = a.order[li];
+    const int64_t p0 = a.ptr[row];
+    const int64_t deg = a.deg[row];
+    float* xo = a.X + row * k;
+    if (deg == 0) {  // nothing survived: Spark leaves such a row out, here it is zero
+      for (int i = tid; i < k; i += NT) xo[i] = 0.f;
+      continue;
+    }
+    // ---- build ----
+    double acc[NB][NB];
+#pragma unroll
+    for (int ia = 0; ia < NB; ++ia)
+#pragma unroll
+      for (int ib = 0; ib < NB; ++ib) acc[ia][ib] = 0.0;
+    double bacc = 0.0, npos = 0.0;
+    for (int64_t t0 = 0; t0 < deg; t0 += FOLD_TILE) {
+      const int nt = deg - t0 < FOLD_TILE ? (int)(deg - t0) : FOLD_TILE;
+      float4 v[PER];
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int e = tid + u * NT, r = e / Q, c4 = e % Q;
+        v[u] = r < nt ? *reinterpret_cast<const float4*>(a.Y + (int64_t)a.col[p0 + t0 + r] * KP + 4 * c4)
+                      : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      __syncthreads();  // the tile's (or the last row's triangle's and solution's) readers are done
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int e = tid + u * NT;
+        *reinterpret_cast<float4*>(tile + 4 * e) = v[u];
+      }
+      if (tid < FOLD_TILE) {
+        const float r = tid < nt ? a.val[p0 + t0 + tid] : 0.f;
+        double c, w, pos;
+        if (a.implicit) {
+          c = a.alpha * (double)fabsf(r);
+          w = r > 0.f ? 1.0 + c : 0.0;
+          pos = r > 0.f ? 1.0 : 0.0;
+        } else {
+          c = tid < nt ? 1.0 : 0.0;
+          w = (double)r;
+          pos = c;
+        }
+        cw[tid] = c;
+        ww[tid] = w;
+        pw[tid] = pos;
+      }
+      __syncthreads();
+      for (int r = 0; r < nt; ++r) {
+        const float* y = tile + r * KP;
+        const double c = cw[r];
+        float yi[NB], ym[NB];  // widened where they are used: the sums take the registers
+#pragma unroll
+        for (int q = 0; q < NB; ++q) {
+          yi[q] = y[ty + TS * q];
+          ym[q] = y[tx + TS * q];
+        }
+#pragma unroll
+        for (int ia = 0; ia < NB; ++ia) {
+          const double cy = c * (double)yi[ia];
+#pragma unroll
+          for (int ib = 0; ib <= ia; ++ib) acc[ia][ib] += cy * (double)ym[ib];
+        }
+        if (tid < KP) bacc += ww[r] * (double)y[tid];
+        npos += pw[r];
+      }
+    }
+    const double ln = a.reg * npos;
+#pragma unroll
+    for (int ia = 0; ia < NB; ++ia)
+#pragma unroll
+      for (int ib = 0; ib <= ia; ++ib) {
+        const int i = ty + TS * ia, m = tx + TS * ib;
+        if (m > i || i >= k) continue;
+        if (a.G) acc[ia][ib] += a.G[(size_t)i * KP + m];
+        if (i == m) acc[ia][ib] += ln;
+      }
+    if (tid < KP) vec[tid] = bacc;
+    // ---- A = L Lᵀ, right-looking, in the registers that built A ----
+    // Column j: its owners (tx = j mod TS) put it into LDS, every thread reads the pivot and the entries of
+    // its own rows and columns, and updates its part of the trailing triangle in registers; the owners leave
+    // the finished column of L in the packed triangle for the substitutions.  One barrier per column: the
+    // column buffer alternates, so column j + 2 is written only after every thread has passed barrier j + 1.
+    bool ok = true;
+#pragma unroll
+    for (int jb = 0; jb < NB; ++jb) {
+      const int jend = !ok ? 0 : (k - jb * TS < TS ? k - jb * TS : TS);
+      for (int jj = 0; jj < jend; ++jj) {
+        const int j = jb * TS + jj;
+        double* cb = colb + (j & 1) * KP;
+        if (tx == jj) {
+#pragma unroll
+          for (int ia = jb; ia < NB; ++ia) {
+            const int i = ty + TS * ia;
+            if (i >= j && i < k) cb[i] = acc[ia][jb];
+          }
+        }
+        __syncthreads();  // also: the last tile is read, the triangle may take its place
+        const double d = cb[j];  // the same value in every thread: the exit is uniform
+        if (!(d > 0.0)) {
+          ok = false;
+          break;
+        }
+        const double rs = 1.0 / sqrt(d);
+        double li[NB], lm[NB];
+#pragma unroll
+        for (int q = jb; q < NB; ++q) {
+          const int i = ty + TS * q, m = tx + TS * q;
+          li[q] = i > j && i < k ? cb[i] * rs : 0.0;
+          lm[q] = m > j && m < k ? cb[m] * rs : 0.0;
+        }
+#pragma unroll
+        for (int ia = jb; ia < NB; ++ia)
+#pragma unroll
+          for (int ib = jb; ib <= ia; ++ib) acc[ia][ib] -= li[ia] * lm[ib];
+        if (tx == jj) {
+#pragma unroll
+          for (int ia = jb; ia < NB; ++ia) {
+            const int i = ty + TS * ia;
+            if (i > j && i < k) A[tri_at(i, j)] = li[ia];
+          }
+        }
+        // L z = b rides along: vec[j] is final once column j - 1 has been applied (before this column's barrier)
+        const double z = vec[j] * rs;
+        if (tid > j && tid < k) vec[tid] -= cb[tid] * rs * z;
+        if (tid == 0) {
+          zb[j] = z;
+          dinv[j] = rs;
+        }
+      }
+    }
+    __syncthreads();
+    if (!ok) {
+      if (tid == 0) atomicMin(a.bad, (int)row);
+      continue;
+    }
+    // ---- Lᵀ x = z (x in vec) ----
+    for (int j = k - 1; j >= 0; --j) {
+      const double x = zb[j] * dinv[j];
+      for (int m = tid; m < j; m += NT) zb[m] -= A[tri_at(j, m)] * x;
+      if (tid == 0) vec[j] = x;
+      __syncthreads();
+    }
+    for (int i = tid; i < k; i += NT) xo[i] = (float)vec[i];
+  }
+}
+
+template <int KP, int TS, bool TRI_LDS>
+hipError_t fold_launch(const FoldArgs& a, int n_wg, hipStream_t s) {
+  constexpr size_t lds = fold_lds_bytes(KP, TRI_LDS);
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fold_solve_kernel<KP, TS, TRI_LDS>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  fold_solve_kernel<KP, TS, TRI_LDS><<<n_wg, TS * TS, lds, s>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+size_t fold_sort_temp_bytes(int64_t n) {
+  size_t a = 0, b = 0, c = 0, d = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (float*)nullptr, (float*)nullptr,
+                                  (size_t)n, 0, 64, (hipStream_t)0);
+  (void)rocprim::run_length_encode(nullptr, b, (uint32_t*)nullptr, (size_t)n, (uint32_t*)nullptr, (int32_t*)nullptr,
+                                   (int64_t*)nullptr, (hipStream_t)0);
+  (void)rocprim::exclusive_scan(nullptr, c, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1,
+                                rocprim::plus<int64_t>(), (hipStream_t)0);
+  (void)rocprim::radix_sort_pairs_desc(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
+                                       (int32_t*)nullptr, (size_t)n, 0, 32, (hipStream_t)0);
+  return std::max(std::max(a, b), std::max(c, d));
+}
+
+hipError_t fold_build_csr(const int32_t* row_id, const int32_t* src_id, const float* rating, int64_t n,
+                          const int32_t* src_ids, int64_t n_src, void* temp, size_t temp_bytes, const FoldCsr& f,
+                          int64_t* n_rows_host, hipStream_t s) {
+  if (n <= 0 || n > (int64_t)0x7FFFFFFF || n_src >= (int64_t)FOLD_DROPPED) return hipErrorInvalidValue;
+  fold_key_kernel<<<fold_grid(n), 256, 0, s>>>(row_id, src_id, n, src_ids, n_src, f.key);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  size_t tb = temp_bytes;
+  e = rocprim::radix_sort_pairs(temp, tb, f.key, f.key_sorted, rating, f.val_sorted, (size_t)n, 0, 64, s);
+  if (e != hipSuccess) return e;
+  fold_split_kernel<<<fold_grid(n), 256, 0, s>>>(f.key_sorted, n, f.hi, f.col);
+  e = hipMemsetAsync(f.counts, 0, (size_t)(n + 1) * 4, s);
+  if (e != hipSuccess) return e;
+  tb = temp_bytes;
+  e = rocprim::run_length_encode(temp, tb, f.hi, (size_t)n, f.runs, f.counts, f.n_rows, s);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(n_rows_host, f.n_rows, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return e;
+  const int64_t nr = *n_rows_host;
+  if (nr <= 0 || nr > n) return hipErrorInvalidValue;
+  tb = temp_bytes;
+  e = rocprim::exclusive_scan(temp, tb, f.counts, f.ptr, (int64_t)0, (size_t)nr + 1, rocprim::plus<int64_t>(), s);
+  if (e != hipSuccess) return e;
+  fold_rows_kernel<<<fold_grid(nr), 256, 0, s>>>(f.runs, f.ptr, f.col, nr, f.ids, f.deg);
+  fold_iota_kernel<<<fold_grid(nr), 256, 0, s>>>(f.iota, nr);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  tb = temp_bytes;
+  return rocprim::radix_sort_pairs_desc(temp, tb, f.deg, f.deg_sorted, f.iota, f.order, (size_t)nr, 0, 32, s);
+}
+
+// KP = 64: one wave per row (its barriers cost nothing) and 19 KB of LDS, eight rows per CU; KP = 128: 69 KB
+// of LDS, two per CU; KP = 256: 1024 threads at the registers of the build, one per CU
+int fold_workgroups(int KP, int64_t n_rows, int n_cu) {
+  int64_t wgs = (int64_t)n_cu * (KP == 64 ? 8 : KP == 128 ? 2 : 1);
+  const char* e = std::getenv("ALBEDO_FOLD_WGS");
+  if (e && *e && std::atoll(e) > 0) wgs = std::min<int64_t>(wgs, std::atoll(e));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(wgs, n_rows));
+}
+
+size_t fold_scratch_doubles(int KP, int n_wg) { return KP == 256 ? (size_t)n_wg * fold_tri(256) : 0; }
+
+hipError_t launch_fold_solve(int KP, const FoldArgs& a, int n_wg, hipStream_t s) {
+  if (a.n_rows <= 0) return hipSuccess;
+  if (n_wg <= 0 || a.k <= 0 || a.k > KP || a.n_rows > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+  if (KP == 64) return fold_launch<64, 8, true>(a, n_wg, s);
+  if (KP == 128) return fold_launch<128, 16, true>(a, n_wg, s);
+  if (KP == 256) return a.scratch ? fold_launch<256, 32, false>(a, n_wg, s) : hipErrorInvalidValue;
+  return hipErrorInvalidValue;
+}
+
+}  // namespace albedo

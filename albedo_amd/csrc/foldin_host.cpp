@@ -1,0 +1,187 @@
+// als_fold_in: host side of the fold-in (foldin.hip).  The call brings the src side's factors into the
+// original basis, takes the fp64 src Gram from the side's fold-in cache (or forms it there), turns the
+// triples into a CSR on the device and solves every distinct row.  It reads the model and writes nothing
+// of it: no factor, basis, Gram, timing or path counter of a half-sweep changes.  Every buffer but the
+// cached Gram (Side::d_foldG) is owned by the call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "albedo_als.h"
+#include "engine.h"
+#include "kernels.h"
+
+using namespace albedo;
+
+namespace {
+
+// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
+// the queued ones before the buffers go
+struct Drain {
+  hipStream_t s;
+  ~Drain() {
+    if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+struct Marks {  // stage marks on the stream
+  hipEvent_t e[4] = {};
+  Marks() = default;
+  Marks(const Marks&) = delete;
+  Marks& operator=(const Marks&) = delete;
+  ~Marks() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t mark(int i, hipStream_t s) {
+    hipError_t r = hipEventCreate(&e[i]);
+    if (r != hipSuccess) return r;
+    return hipEventRecord(e[i], s);
+  }
+};
+
+int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_t n, const int32_t* row_id,
+            const int32_t* src_id, const float* rating, int64_t cap, int64_t* n_rows_out, int32_t* ids_out,
+            int64_t* degree_out, float* factors_out) {
+  Side& S = c->s[1 - side];
+  const int KP = c->KP, k = c->p.rank;
+  hipStream_t st = c->st;
+  TRYC(materialize(c, 1 - side));
+  DevBuf d_row, d_src, d_val, d_sids, d_key, d_keys, d_vals, d_hi, d_col, d_runs, d_cnt, d_ptr, d_nr, d_ids, d_deg, d_degs;
+  DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad, d_X;
+  Marks clk;
+  Drain queued{st};
+  for (DevBuf* b : {&d_row, &d_src, &d_val, &d_vals, &d_hi, &d_col, &d_runs, &d_ids, &d_deg, &d_degs, &d_iota, &d_order})
+    HIPCHK(b->ensure((size_t)n * 4));
+  HIPCHK(d_cnt.ensure((size_t)(n + 1) * 4));
+  HIPCHK(d_key.ensure((size_t)n * 8));
+  HIPCHK(d_keys.ensure((size_t)n * 8));
+  HIPCHK(d_ptr.ensure((size_t)(n + 1) * 8));
+  HIPCHK(d_nr.ensure(8));
+  HIPCHK(d_bad.ensure(4));
+  HIPCHK(d_sids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));
+  const size_t tb = fold_sort_temp_bytes(n);
+  HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
+  HIPCHK(hipMemcpyAsync(d_row.p, row_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_src.p, src_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_val.p, rating, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_sids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
+  const int bad0 = INT_MAX;
+  HIPCHK(hipMemcpyAsync(d_bad.p, &bad0, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(clk.mark(0, st));
+  FoldCsr f{};
+  f.key = d_key.as<uint64_t>();
+  f.key_sorted = d_keys.as<uint64_t>();
+  f.val_sorted = d_vals.as<float>();
+  f.hi = d_hi.as<uint32_t>();
+  f.col = d_col.as<uint32_t>();
+  f.runs = d_runs.as<uint32_t>();
+  f.counts = d_cnt.as<int32_t>();
+  f.ptr = d_ptr.as<int64_t>();
+  f.n_rows = d_nr.as<int64_t>();
+  f.ids = d_ids.as<int32_t>();
+  f.deg = d_deg.as<uint32_t>();
+  f.deg_sorted = d_degs.as<uint32_t>();
+  f.iota = d_iota.as<int32_t>();
+  f.order = d_order.as<int32_t>();
+  int64_t nr = 0;
+  HIPCHK(fold_build_csr(d_row.as<int32_t>(), d_src.as<int32_t>(), d_val.as<float>(), n, d_sids.as<int32_t>(), S.n,
+                        d_tmp.p, tb, f, &nr, st));
+  HIPCHK(clk.mark(1, st));
+  const bool form_gram = implicit && !S.fold_gram_valid;
+  if (form_gram) {  // into the side's own buffer: c->d_G belongs to the half-sweeps
+    const int nblk = audit_gram_blocks(S.n);
+    HIPCHK(d_slab.ensure((size_t)nblk * KP * KP * 8));
+    HIPCHK(S.d_foldG.ensure((size_t)KP * KP * 8));
+    HIPCHK(launch_audit_gram(KP, S.d_orig.as<float>(), S.n, d_slab.as<double>(), nblk, S.d_foldG.as<double>(), st));
+  }
+  HIPCHK(clk.mark(2, st));
+  const int n_wg = fold_workgroups(KP, nr, c->n_cu);
+  const size_t sd = fold_scratch_doubles(KP, n_wg);
+  if (sd) HIPCHK(d_scratch.ensure(sd * 8));
+  HIPCHK(d_X.ensure((size_t)nr * k * 4));
+  FoldArgs a{};
+  a.Y = S.d_orig.as<float>();
+  a.G = implicit ? S.d_foldG.as<double>() : nullptr;
+  a.ptr = f.ptr;
+  a.deg = f.deg;
+  a.col = f.col;
+  a.val = f.val_sorted;
+  a.order = f.order;
+  a.n_rows = nr;
+  a.k = k;
+  a.implicit = implicit;
+  a.alpha = alpha;
+  a.reg = reg;
+  a.scratch = sd ? d_scratch.as<double>() : nullptr;
+  a.bad = d_bad.as<int>();
+  a.X = d_X.as<float>();
+  HIPCHK(launch_fold_solve(KP, a, n_wg, st));
+  HIPCHK(clk.mark(3, st));
+  int bad = INT_MAX;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (form_gram) S.fold_gram_valid = true;
+  c->fold_ms[0] = event_ms(clk.e[0], clk.e[1]);
+  c->fold_ms[1] = form_gram ? event_ms(clk.e[1], clk.e[2]) : 0.0;
+  c->fold_ms[2] = event_ms(clk.e[2], clk.e[3]);
+  c->fold_ms[3] = event_ms(clk.e[0], clk.e[3]);
+  *n_rows_out = nr;
+  if (bad != INT_MAX) {
+    int32_t id = 0;
+    HIPCHK(copy_st(c, &id, f.ids + bad, 4, hipMemcpyDeviceToHost));
+    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
+                "LAPACK.dppsv-equivalent Cholesky met a non-positive pivot because A is not positive definite. Is A "
+                "derived from a singular matrix (e.g. collinear column values)? (fold-in of " +
+                    std::string(side == ALS_USER ? "user" : "item") + " " + std::to_string(id) +
+                    ", the lowest failing id)");
+  }
+  if (nr > cap) return ALS_OK;
+  if (ids_out) HIPCHK(copy_st(c, ids_out, d_ids.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+  if (degree_out) {
+    std::vector<uint32_t> deg(nr);
+    HIPCHK(copy_st(c, deg.data(), d_deg.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < nr; ++r) degree_out[r] = deg[r];
+  }
+  if (factors_out) HIPCHK(copy_st(c, factors_out, d_X.p, (size_t)nr * k * 4, hipMemcpyDeviceToHost));
+  return ALS_OK;
+}
+
+}  // namespace
+
+extern "C" int als_fold_in(als_ctx* c, int side, const als_fold_params* fp, int64_t n, const int32_t* row_id,
+                           const int32_t* src_id, const float* rating, int64_t cap, int64_t* n_rows_out,
+                           int32_t* ids_out, int64_t* degree_out, float* factors_out) {
+  if (!c || (side != 0 && side != 1) || n < 0 || !n_rows_out || (n > 0 && (!row_id || !src_id || !rating)))
+    return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  if (fp && (std::isnan(fp->reg_param) || fp->reg_param < 0.0 || std::isnan(fp->alpha) || fp->alpha < 0.0))
+    return fail(ALS_E_INVALID_ARGUMENT, "als_fold_in: regParam and alpha should be >= 0");
+  if (!fp && c->model_only)
+    return fail(ALS_E_INVALID_ARGUMENT,
+                "als_fold_in: a model-only context has no regParam, alpha or implicitPrefs: pass als_fold_params");
+  if (c->p.nonnegative) return fail(ALS_E_UNSUPPORTED, "als_fold_in does not support nonnegative = true (NNLS)");
+  if (c->world > 1) return fail(ALS_E_UNSUPPORTED, "als_fold_in is single-process (world = 1)");
+  if (n > (int64_t)0x7FFFFFFF) return fail(ALS_E_UNSUPPORTED, "als_fold_in takes at most 2^31 - 1 triples a call");
+  *n_rows_out = 0;
+  for (double& v : c->fold_ms) v = 0.0;
+  if (n == 0) return ALS_OK;
+  if (!c->s[1 - side].has_factors)
+    return fail(ALS_E_STATE, std::string("als_fold_in needs the ") + (side == ALS_USER ? "item" : "user") +
+                                 " factors (fit, inject or load them first)");
+  TRYC(set_device(c));
+  const double reg = fp ? fp->reg_param : c->p.reg_param, alpha = fp ? fp->alpha : c->p.alpha;
+  const int implicit = fp ? fp->implicit_prefs != 0 : c->p.implicit_prefs != 0;
+  return fold_in(c, side, reg, alpha, implicit, n, row_id, src_id, rating, cap, n_rows_out, ids_out, degree_out,
+                 factors_out);
+}
+
+extern "C" int als_fold_in_timing(const als_ctx* c, double* out4) {
+  if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  for (int i = 0; i < 4; ++i) out4[i] = c->fold_ms[i];
+  return ALS_OK;
+}

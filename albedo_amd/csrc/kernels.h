@@ -1,5 +1,5 @@
 // Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
-// eval_host.cpp, audit_host.cpp) and the HIP kernels.
+// eval_host.cpp, audit_host.cpp, foldin_host.cpp) and the HIP kernels.
 // Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -326,6 +326,47 @@ hipError_t launch_audit_rows(int KP, const AuditArgs& g, int64_t l0, int64_t n_l
 // rows with !(eta <= tol), non-finite and negative counts, the worst row and Σ eta, added in a fixed order
 hipError_t launch_audit_summary(const double* eta, const int32_t* neg, int64_t n, double tol, AuditSummary* part,
                                 AuditSummary* out, hipStream_t s);
+
+// ---- fold-in (foldin.hip): factors of new rows from the frozen other side (als_fold_in) ----------------
+constexpr int FOLD_TILE = 32;  // ratings gathered into LDS per build step
+// The triples as a CSR over the distinct row ids.  Sort key: the row id (sign bit flipped) above the src
+// row, 0xFFFFFFFF for a src id the model does not know, so a row's dropped triples end its range.
+struct FoldCsr {
+  uint64_t *key, *key_sorted;  // [n]
+  float* val_sorted;           // [n] ratings in key order
+  uint32_t *hi, *col;          // [n] the two halves of the sorted keys: row key, src row
+  uint32_t* runs;              // [n] distinct row keys, ascending
+  int32_t* counts;             // [n + 1] triples per row, dropped ones included
+  int64_t* ptr;                // [n + 1] first triple of each row
+  int64_t* n_rows;             // device count of distinct rows
+  int32_t* ids;                // [n] raw id of each row
+  uint32_t *deg, *deg_sorted;  // [n] surviving triples per row
+  int32_t *iota, *order;       // [n] order: the rows by descending degree (ties: ascending id)
+};
+size_t fold_sort_temp_bytes(int64_t n);
+// map + sort + run lengths + degrees + solve order of n > 0 triples; *n_rows_host is valid on return
+hipError_t fold_build_csr(const int32_t* row_id, const int32_t* src_id, const float* rating, int64_t n,
+                          const int32_t* src_ids, int64_t n_src, void* temp, size_t temp_bytes, const FoldCsr& f,
+                          int64_t* n_rows_host, hipStream_t s);
+struct FoldArgs {
+  const float* Y;         // src factors in the original basis, [n_src][KP]
+  const double* G;        // fp64 src Gram [KP][KP] (implicit), null when explicit
+  const int64_t* ptr;     // FoldCsr::ptr
+  const uint32_t* deg;    // FoldCsr::deg: the first deg[r] triples of row r are the live ones
+  const uint32_t* col;
+  const float* val;
+  const int32_t* order;   // list position -> row
+  int64_t n_rows;
+  int k;                  // the model rank: the system is k x k
+  int implicit;
+  double alpha, reg;
+  double* scratch;        // KP = 256: fold_scratch_doubles of packed triangles, one per workgroup
+  int* bad;               // atomicMin of the rows that met a pivot <= 0 or NaN (caller sets it to INT_MAX)
+  float* X;               // out [n_rows][k], row order (degree-0 rows: zeros)
+};
+int fold_workgroups(int KP, int64_t n_rows, int n_cu);  // the persistent grid (ALBEDO_FOLD_WGS caps it)
+size_t fold_scratch_doubles(int KP, int n_wg);
+hipError_t launch_fold_solve(int KP, const FoldArgs& a, int n_wg, hipStream_t s);
 
 // Ingest (ingest.hip): COO -> remap + CSR.
 struct DeviceBuf;

@@ -270,6 +270,7 @@ int albedo::factor_buffers(als_ctx* c) {
     S.has_gram = false;
     S.has_factors = false;
     S.orig_valid = false;
+    S.fold_gram_valid = false;
     S.full_valid = false;
   }
   const int64_t maxsrc = std::max(c->s[0].own_n, c->s[1].own_n);
@@ -844,6 +845,7 @@ int finish_half(als_ctx* c, int t, const Prepared& P) {
   if (nnls) HIPCHK(hipMemcpyAsync(T.d_B.p, S.d_B.p, (size_t)KP * KP * 8, hipMemcpyDeviceToDevice, st));  // no rotation
   T.has_factors = true;
   T.orig_valid = false;
+  T.fold_gram_valid = false;
   T.full_valid = multi && !nnls;  // Cholesky: gathered behind the solve (st2); the next half waits for it
   return ALS_OK;
 }

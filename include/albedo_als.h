@@ -211,6 +211,49 @@ int als_eval_pairs_timing(const als_ctx* ctx, double* out5);
 /* ALSModel.transform: F2J sdot per (user, item) pair; NaN when either id is unknown. */
 int als_predict(als_ctx* ctx, int64_t n, const int32_t* user, const int32_t* item, float* out);
 
+/* ---- fold-in: factors for rows the fit did not see ---------------------------------------------- */
+typedef struct als_fold_params {   /* the normal equation's parameters, as als_params */
+  double reg_param, alpha;
+  int32_t implicit_prefs, reserved;   /* reserved = 0 */
+} als_fold_params;
+/* The factors of new rows of `side` from their (row_id, src_id, rating) triples, each row solved against
+ * the current factors of the other side, which stay frozen ("recalculate user"): side = ALS_USER gives new
+ * users from (user, item, rating) triples and the item factors, ALS_ITEM is the mirror.  The factor of row
+ * j is what Spark's computeFactors gives that row from these src factors: with G the fp64 Gram of all src
+ * rows (implicit prefs; 0 otherwise) and c, w, n as als_audit_rows defines them,
+ *   (G + sum_i c_i y_i y_i^T + regParam·n_j·I) x_j = sum_i w_i y_i
+ * built and solved by Cholesky in fp64, in the original basis (the src factors are what als_get_factors
+ * returns), at the model rank, and rounded to fp32.
+ * The model is read-only: the context's factors, bases, Gram state, timings and path stats are unchanged,
+ * and a fold-in between two half-sweeps leaves the fit bit-identical.  row_id is any int32; it may
+ * coincide with an id the model already has on that side: the call then recomputes that row and stores
+ * nothing.  One output row per distinct row_id, in ascending id order; *n_rows_out is their count.
+ * ids_out / degree_out [cap] and factors_out [cap][rank] are each filled when non-null and
+ * *n_rows_out <= cap; cap = n always suffices.  A triple whose src_id the model does not know is dropped;
+ * degree_out is the number of surviving triples of the row, and a row left with none gets an all-zero
+ * factor.  A repeated (row, src) pair counts once per copy, as in the ingest.  The triples of a row are
+ * summed in ascending src-row order, so the result does not depend on the order of the input arrays
+ * (except among copies of one pair with different ratings); no floating-point atomics are used and two
+ * calls give identical bits.
+ * fp == NULL means the context's own regParam, alpha and implicitPrefs.  A context from als_model_create
+ * has none (Spark's saved ALSModel carries only the rank) and requires fp.
+ * Errors: ALS_E_UNSUPPORTED for a context with nonnegative = true (NNLS fold-in is not implemented), for
+ * world > 1 and for n >= 2^31; ALS_E_STATE when the src side has no factors; ALS_E_INVALID_ARGUMENT for
+ * a bad side, a negative n, a NaN or negative reg_param / alpha, null inputs with n > 0, a null
+ * n_rows_out, and fp == NULL on a model-only context.  n = 0 is ALS_OK with *n_rows_out = 0.  Forks may
+ * call it.  A pivot <= 0 or NaN (regParam·n = 0 on a singular system) fails the call with
+ * ALS_E_NOT_POSITIVE_DEFINITE; the message names the lowest failing raw id, and the outputs are then
+ * unspecified.  The fp64 src Gram is kept per side until that side's factors change, so further calls
+ * (one user at a time on a serving context) skip it.  ALBEDO_FOLD_WGS in the environment caps the
+ * persistent grid of the solve (one workgroup per row). */
+int als_fold_in(als_ctx* ctx, int side, const als_fold_params* fp,
+                int64_t n, const int32_t* row_id, const int32_t* src_id, const float* rating,
+                int64_t cap, int64_t* n_rows_out, int32_t* ids_out, int64_t* degree_out,
+                float* factors_out /* [cap][rank] */);
+/* Device time of the last als_fold_in call from HIP events on the context's stream (ms): out[0] = id
+ * mapping + sort + CSR, out[1] = src Gram (0 when taken from the cache), out[2] = solve, out[3] = total. */
+int als_fold_in_timing(const als_ctx* ctx, double* out4);
+
 /* ---- observability ---------------------------------------------------------------------------- */
 /* Per-stage device time (ms) of the last half-sweeps: see ALS_T_* indices. n = array length. */
 enum {
