@@ -133,6 +133,8 @@ SIGNATURES = [
     ("als_fold_in", C.c_int, [P, C.c_int, C.POINTER(als_fold_params), C.c_int64, I32P, I32P, F32P, C.c_int64, I64P, I32P,
                               I64P, F32P]),
     ("als_fold_in_timing", C.c_int, [P, F64P]),
+    ("als_recommend_vectors", C.c_int, [P, C.c_int, C.c_int32, C.c_int64, F32P, I64P, I32P, I32P, F32P]),
+    ("als_recommend_vectors_timing", C.c_int, [P, F64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
     ("als_evaluate_ranking", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P,
                                        C.c_int64]),
@@ -240,4 +242,52 @@ def fold_in_timing(ctx):
 
     out = np.zeros(4, dtype=np.float64)
     check(load().als_fold_in_timing(ctx, ptr(out, C.c_double)))
+    return out
+
+
+def exclusion_csr(exclude, n_q):
+    """The (ptr int64 [n_q + 1], ids int32) pair als_recommend_vectors takes, from None, a (ptr, ids) pair or
+    a list of n_q id arrays."""
+    import numpy as np
+
+    if exclude is None:
+        return None, None
+    if isinstance(exclude, tuple):  # a tuple is always the pair; id lists come in a list
+        if len(exclude) != 2 or len(exclude[0]) != n_q + 1:
+            raise ValueError(f"exclude as a tuple should be (ptr [{n_q + 1}], ids)")
+        return np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)
+    if len(exclude) != n_q:
+        raise ValueError(f"exclude should hold one id list per query: {len(exclude)} lists, {n_q} queries")
+    lists = [np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+    ptr_ = np.zeros(n_q + 1, dtype=np.int64)
+    np.cumsum([e.size for e in lists], out=ptr_[1:])
+    ids = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+    return ptr_, np.ascontiguousarray(ids, dtype=np.int32)
+
+
+def recommend_vectors(ctx, side, vectors, k, rank, exclude=None):
+    """als_recommend_vectors on the context handle `ctx`: (dst ids [n_q, k], scores [n_q, k]) of the query
+    vectors [n_q, rank] against the factors of `side`, -1 / NaN padded."""
+    import numpy as np
+
+    q = np.ascontiguousarray(vectors, dtype=np.float32)
+    if q.ndim != 2 or q.shape[1] != rank:
+        raise ValueError(f"vectors should be [n, {rank}], not {q.shape}")
+    n_q = int(q.shape[0])
+    ptr_, eids = exclusion_csr(exclude, n_q)
+    ids = np.empty((n_q, max(int(k), 0)), dtype=np.int32)
+    sc = np.empty((n_q, max(int(k), 0)), dtype=np.float32)
+    check(load().als_recommend_vectors(ctx, side, int(k), n_q, ptr(q, C.c_float),
+                                       ptr(ptr_, C.c_int64) if ptr_ is not None else None,
+                                       ptr(eids, C.c_int32) if eids is not None and eids.size else None,
+                                       ptr(ids, C.c_int32), ptr(sc, C.c_float)))
+    return ids, sc
+
+
+def recommend_vectors_timing(ctx):
+    """als_recommend_vectors_timing: device ms of the last call: [exclusion map + sort, scan, merge, total]."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.float64)
+    check(load().als_recommend_vectors_timing(ctx, ptr(out, C.c_double)))
     return out

@@ -398,8 +398,19 @@ class ALSModel(_Params):
     def recommendForAllItems(self, numUsers):
         return self._rec_frame(*self._recommend(_lib.ALS_ITEM, numUsers), self._p["itemCol"], self._p["userCol"])
 
-    def recommendForUserSubset(self, dataset, numItems):
+    def recommendForUserSubset(self, dataset, numItems, exclude=None):
+        """Spark's recommendForUserSubset.  exclude: a frame of (userCol, itemCol) rows; each user's lists then
+        leave out the items the frame gives them (their factors go through als_recommend_vectors as queries)."""
         users = _column(dataset, self._p["userCol"])
+        if exclude is not None:
+            uid, U = self.user_factors_np()
+            sub = np.unique(_checked_cast(users, self._p["userCol"]))
+            at = np.minimum(np.searchsorted(uid, sub), max(uid.size - 1, 0))
+            known = uid[at] == sub if uid.size else np.zeros(sub.size, bool)  # unknown users get no row
+            sub, at = sub[known], at[known]
+            excl = self._exclusions(sub, _column(exclude, self._p["userCol"]), _column(exclude, self._p["itemCol"]))
+            ids, sc = self.recommend_vectors_np(U[at], numItems, excl, "item")
+            return self._rec_frame(sub, ids, sc, self._p["userCol"], self._p["itemCol"])
         return self._rec_frame(*self._recommend(_lib.ALS_USER, numItems, users), self._p["userCol"],
                                self._p["itemCol"])
 
@@ -582,13 +593,61 @@ class ALSModel(_Params):
                                     _column(dataset, self._p["ratingCol"]), t, regParam, alpha, implicitPrefs)
         return self._frame(ids, f)
 
-    def recommendForNewUsers(self, dataset, numItems, **fold_kw):
+    def _exclusions(self, ids, users, items):
+        """(ptr, item ids) for als_recommend_vectors: for each of the ascending user ids, their items among the
+        (user, item) rows."""
+        u = _checked_cast(users, self._p["userCol"])
+        it = _checked_cast(items, self._p["itemCol"])
+        if u.size != it.size:
+            raise ValueError("the user and item columns must have the same length")
+        o = np.argsort(u, kind="stable")
+        us = u[o]
+        ptr_ = np.zeros(len(ids) + 1, np.int64)
+        np.cumsum(np.searchsorted(us, ids, "right") - np.searchsorted(us, ids, "left"), out=ptr_[1:])
+        keep = o[np.isin(us, ids)]  # sorted by user like ids: the rows of other users are left out
+        return ptr_, np.ascontiguousarray(it[keep], dtype=np.int32)
+
+    def recommend_vectors_np(self, vectors, num, exclude=None, side="item"):
+        """(dst ids [n, num], scores [n, num]) of the exact top-num of each row of `vectors` [n, rank] against
+        the factors of `side` ("item": items are recommended; "user": users), sorted (score desc, id asc) with
+        -1 / NaN padding (als_recommend_vectors; num <= 64).  The score is the F2J dot product of the vector
+        and the row's factor.  exclude: one array of raw dst ids per vector (a list), or a (ptr, ids) tuple in
+        CSR form; those rows are not listed.  Unknown and repeated ids are ignored."""
+        return _lib.recommend_vectors(self._h, self._side(side), vectors, num, self.rank, exclude)
+
+    def recommendForVectors(self, ids, vectors, num, exclude=None, side="item"):
+        """recommend_vectors_np as the usual recommendation frame: `ids` label the vectors (the userCol column
+        when items are recommended, the itemCol column with side="user")."""
+        t = self._side(side)
+        src_col, dst_col = ((self._p["userCol"], self._p["itemCol"]) if t == _lib.ALS_ITEM
+                            else (self._p["itemCol"], self._p["userCol"]))
+        src = np.asarray(ids)
+        if src.ndim != 1 or src.shape[0] != np.shape(vectors)[0]:
+            raise ValueError("ids should be one-dimensional, one per vector")
+        dst, sc = self.recommend_vectors_np(vectors, num, exclude, t)
+        return self._rec_frame(src, dst, sc, src_col, dst_col)
+
+    def recommend_vectors_timing(self):
+        """Device ms of the last recommend_vectors_np: exclusions (map + sort), scan, merge, total."""
+        return dict(zip(("exclusions", "scan", "merge", "total"), _lib.recommend_vectors_timing(self._h).tolist()))
+
+    def recommendForNewUsers(self, dataset, numItems, excludeKnown=False, **fold_kw):
         """recommendForUserSubset for users the model has not seen: their factors are folded in from
-        `dataset` (foldIn's keywords apply), then scored against the model's items."""
-        lib = load()
+        `dataset` (foldIn's keywords apply), then scored against the model's items on the model's own
+        context (als_recommend_vectors).  excludeKnown: a user's lists leave out their items in `dataset`.
+        numItems > 64 is served by als_recommend on a transient context, without excludeKnown."""
         self._fold_params(*(fold_kw.get(k) for k in ("regParam", "alpha", "implicitPrefs")))
-        ids, _, f = self.fold_in_np(_column(dataset, self._p["userCol"]), _column(dataset, self._p["itemCol"]),
-                                    _column(dataset, self._p["ratingCol"]), _lib.ALS_USER, **fold_kw)
+        users, items = _column(dataset, self._p["userCol"]), _column(dataset, self._p["itemCol"])
+        ids, _, f = self.fold_in_np(users, items, _column(dataset, self._p["ratingCol"]), _lib.ALS_USER, **fold_kw)
+        if int(numItems) > 64 and not excludeKnown:
+            return self._recommend_transient(ids, f, numItems)
+        excl = self._exclusions(ids, users, items) if excludeKnown else None
+        dst, sc = self.recommend_vectors_np(f, numItems, excl, "item")
+        return self._rec_frame(ids, dst, sc, self._p["userCol"], self._p["itemCol"])
+
+    def _recommend_transient(self, ids, f, numItems):
+        """als_recommend of the given user rows on a model-only context of their own (numItems > 64)."""
+        lib = load()
         ii, itf = self.item_factors_np()
         ii, itf = np.ascontiguousarray(ii), np.ascontiguousarray(itf)
         h = C.c_void_p()

@@ -1,6 +1,7 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in): error reporting, the device buffer, the row buckets, the per-side state, the
+// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in; query_topk_host.cpp:
+// top-k of caller-supplied vectors): error reporting, the device buffer, the row buckets, the per-side state, the
 // context and the few functions one file calls in another.  Not part of the public C ABI
 // (include/albedo_als.h).
 #pragma once
@@ -222,6 +223,8 @@ struct als_ctx {
   double eval_ms[5] = {0, 0, 0, 0, 0};
   // device time of the last als_fold_in call (ms): map + sort + CSR, src Gram, solve, total
   double fold_ms[4] = {0, 0, 0, 0};
+  // device time of the last als_recommend_vectors call (ms): exclusion map + sort, scan, merge, total
+  double query_ms[4] = {0, 0, 0, 0};
   hipEvent_t evt[5] = {};
   // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
   // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was

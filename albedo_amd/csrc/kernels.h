@@ -1,5 +1,5 @@
 // Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
-// eval_host.cpp, audit_host.cpp, foldin_host.cpp) and the HIP kernels.
+// eval_host.cpp, audit_host.cpp, foldin_host.cpp, query_topk_host.cpp) and the HIP kernels.
 // Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -367,6 +367,28 @@ struct FoldArgs {
 int fold_workgroups(int KP, int64_t n_rows, int n_cu);  // the persistent grid (ALBEDO_FOLD_WGS caps it)
 size_t fold_scratch_doubles(int KP, int n_wg);
 hipError_t launch_fold_solve(int KP, const FoldArgs& a, int n_wg, hipStream_t s);
+
+// ---- query top-k (query_topk.hip): exact top-k of caller-supplied vectors (als_recommend_vectors) ------
+constexpr int QT_Q = 16;  // queries a workgroup scores at a time
+struct QueryPlan {
+  int64_t slice_rows, n_slices, n_qtiles;  // grid of the scan: n_slices dst slices x n_qtiles tiles of QT_Q queries
+};
+// slice size from the CU count (ALBEDO_QUERY_SLICE_ROWS in the environment overrides it)
+QueryPlan query_plan(int64_t n_dst, int64_t n_q, int n_cu);
+size_t query_sort_temp_bytes(int64_t n_e);
+// key_sorted [n_e]: (query << 32 | dst row), ascending; row 0xFFFFFFFF for an id the model does not know.
+// excl_ptr [n_q + 1] starts at 0 and ends at n_e (device, like every pointer here)
+hipError_t query_map_exclusions(const int64_t* excl_ptr, int64_t n_q, const int32_t* excl_ids, int64_t n_e,
+                                const int32_t* dst_ids, int64_t n_dst, uint64_t* key, uint64_t* key_sorted, void* temp,
+                                size_t temp_bytes, hipStream_t s);
+// part_score / part_row [n_slices][n_q][k]: each slice's best k per query, row 0xFFFFFFFF past its length.
+// excl_ptr null: no exclusions
+hipError_t launch_query_scan(int KP, int rank, const float* Y, int64_t n_dst, const float* q, int64_t n_q, int k,
+                             const int64_t* excl_ptr, const uint64_t* excl_key, const QueryPlan& p, float* part_score,
+                             uint32_t* part_row, int n_cu, hipStream_t s);
+// ids_out / scores_out [n_q][k]: raw ids and scores in (score desc, row asc) order, -1 / NaN padded
+hipError_t launch_query_merge(const float* part_score, const uint32_t* part_row, int64_t n_slices, int64_t n_q, int k,
+                              const int32_t* dst_ids, int32_t* ids_out, float* scores_out, hipStream_t s);
 
 // Ingest (ingest.hip): COO -> remap + CSR.
 struct DeviceBuf;

@@ -1,0 +1,140 @@
+// als_recommend_vectors: host side of the query top-k (query_topk.hip).  The call checks its arguments,
+// brings the dst side's factors into the original basis, maps and sorts the exclusion lists on the device,
+// scans the dst rows slice by slice and merges the slice partials.  It reads the model and writes nothing of
+// it: no factor, basis, Gram, counter or timing of als_recommend or of a half-sweep changes.  Every buffer
+// is owned by the call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "albedo_als.h"
+#include "engine.h"
+#include "kernels.h"
+
+using namespace albedo;
+
+namespace {
+
+// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
+// the queued ones before the buffers go
+struct Drain {
+  hipStream_t s;
+  ~Drain() {
+    if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+struct Marks {  // stage marks on the stream
+  hipEvent_t e[4] = {};
+  Marks() = default;
+  Marks(const Marks&) = delete;
+  Marks& operator=(const Marks&) = delete;
+  ~Marks() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t mark(int i, hipStream_t s) {
+    hipError_t r = hipEventCreate(&e[i]);
+    if (r != hipSuccess) return r;
+    return hipEventRecord(e[i], s);
+  }
+};
+
+// ptr0: the exclusion ranges shifted to start at 0 ([n_q + 1]), empty when the call has none
+int recommend_vectors(als_ctx* c, int side, int k, int64_t n_q, const float* q, const std::vector<int64_t>& ptr0,
+                      const int32_t* excl_ids, int32_t* ids_out, float* scores_out) {
+  Side& S = c->s[side];
+  const int KP = c->KP, rank = c->p.rank;
+  hipStream_t st = c->st;
+  TRYC(materialize(c, side));
+  const int64_t n_e = ptr0.empty() ? 0 : ptr0.back();
+  const QueryPlan plan = query_plan(S.n, n_q, c->n_cu);
+  DevBuf d_q, d_ids, d_ptr, d_eid, d_key, d_keys, d_tmp, d_ps, d_pr, d_oi, d_os;
+  Marks clk;
+  Drain queued{st};
+  HIPCHK(d_q.ensure((size_t)n_q * rank * 4));
+  HIPCHK(d_ids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));
+  const size_t part = (size_t)plan.n_slices * n_q * k;
+  HIPCHK(d_ps.ensure(part * 4));
+  HIPCHK(d_pr.ensure(part * 4));
+  HIPCHK(d_oi.ensure((size_t)n_q * k * 4));
+  HIPCHK(d_os.ensure((size_t)n_q * k * 4));
+  HIPCHK(hipMemcpyAsync(d_q.p, q, (size_t)n_q * rank * 4, hipMemcpyHostToDevice, st));
+  if (S.n > 0) HIPCHK(hipMemcpyAsync(d_ids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
+  size_t tb = 0;
+  if (n_e > 0) {
+    tb = query_sort_temp_bytes(n_e);
+    HIPCHK(d_ptr.ensure((size_t)(n_q + 1) * 8));
+    HIPCHK(d_eid.ensure((size_t)n_e * 4));
+    HIPCHK(d_key.ensure((size_t)n_e * 8));
+    HIPCHK(d_keys.ensure((size_t)n_e * 8));
+    HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
+    HIPCHK(hipMemcpyAsync(d_ptr.p, ptr0.data(), (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_eid.p, excl_ids, (size_t)n_e * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(clk.mark(0, st));
+  if (n_e > 0)
+    HIPCHK(query_map_exclusions(d_ptr.as<int64_t>(), n_q, d_eid.as<int32_t>(), n_e, d_ids.as<int32_t>(), S.n,
+                                d_key.as<uint64_t>(), d_keys.as<uint64_t>(), d_tmp.p, tb, st));
+  HIPCHK(clk.mark(1, st));
+  HIPCHK(launch_query_scan(KP, rank, S.d_orig.as<float>(), S.n, d_q.as<float>(), n_q, k,
+                           n_e > 0 ? d_ptr.as<int64_t>() : nullptr, n_e > 0 ? d_keys.as<uint64_t>() : nullptr, plan,
+                           d_ps.as<float>(), d_pr.as<uint32_t>(), c->n_cu, st));
+  HIPCHK(clk.mark(2, st));
+  HIPCHK(launch_query_merge(d_ps.as<float>(), d_pr.as<uint32_t>(), plan.n_slices, n_q, k, d_ids.as<int32_t>(),
+                            d_oi.as<int32_t>(), d_os.as<float>(), st));
+  HIPCHK(clk.mark(3, st));
+  HIPCHK(hipMemcpyAsync(ids_out, d_oi.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(scores_out, d_os.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->query_ms[0] = n_e > 0 ? event_ms(clk.e[0], clk.e[1]) : 0.0;
+  c->query_ms[1] = event_ms(clk.e[1], clk.e[2]);
+  c->query_ms[2] = event_ms(clk.e[2], clk.e[3]);
+  c->query_ms[3] = event_ms(clk.e[0], clk.e[3]);
+  return ALS_OK;
+}
+
+}  // namespace
+
+extern "C" int als_recommend_vectors(als_ctx* c, int side, int32_t k, int64_t n_q, const float* q, const int64_t* excl_ptr,
+                                     const int32_t* excl_ids, int32_t* ids_out, float* scores_out) {
+  if (!c || (side != 0 && side != 1) || k < 1 || n_q < 0 || (n_q > 0 && (!q || !ids_out || !scores_out)))
+    return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  if (k > 64) return fail(ALS_E_UNSUPPORTED, "als_recommend_vectors keeps at most 64 rows per query (k <= 64)");
+  if (c->world > 1) return fail(ALS_E_UNSUPPORTED, "als_recommend_vectors is single-process (world = 1)");
+  if (n_q > (int64_t)0x7FFFFFFF)
+    return fail(ALS_E_UNSUPPORTED, "als_recommend_vectors takes at most 2^31 - 1 queries a call");
+  std::vector<int64_t> ptr0;
+  if (excl_ptr && n_q > 0) {
+    if (excl_ptr[0] < 0) return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_vectors: excl_ptr is negative");
+    for (int64_t i = 0; i < n_q; ++i)
+      if (excl_ptr[i + 1] < excl_ptr[i])
+        return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_vectors: excl_ptr does not ascend at query " + std::to_string(i));
+    const int64_t n_e = excl_ptr[n_q] - excl_ptr[0];
+    if (n_e > (int64_t)0x7FFFFFFF)
+      return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_vectors takes at most 2^31 - 1 exclusions a call");
+    if (n_e > 0 && !excl_ids)
+      return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_vectors: excl_ids is null and excl_ptr names a non-empty range");
+    if (n_e > 0) {
+      ptr0.resize((size_t)n_q + 1);
+      for (int64_t i = 0; i <= n_q; ++i) ptr0[i] = excl_ptr[i] - excl_ptr[0];
+      excl_ids += excl_ptr[0];
+    }
+  }
+  for (double& v : c->query_ms) v = 0.0;
+  if (n_q == 0) return ALS_OK;
+  if (!c->s[side].has_factors)
+    return fail(ALS_E_STATE, std::string("als_recommend_vectors needs the ") + (side == ALS_USER ? "user" : "item") +
+                                 " factors (fit, inject or load them first)");
+  TRYC(set_device(c));
+  return recommend_vectors(c, side, k, n_q, q, ptr0, excl_ids, ids_out, scores_out);
+}
+
+extern "C" int als_recommend_vectors_timing(const als_ctx* c, double* out4) {
+  if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  for (int i = 0; i < 4; ++i) out4[i] = c->query_ms[i];
+  return ALS_OK;
+}

@@ -254,6 +254,40 @@ int als_fold_in(als_ctx* ctx, int side, const als_fold_params* fp,
  * mapping + sort + CSR, out[1] = src Gram (0 when taken from the cache), out[2] = solve, out[3] = total. */
 int als_fold_in_timing(const als_ctx* ctx, double* out4);
 
+/* Exact top-k of caller-supplied query vectors against the factors of `dst_side` (ALS_ITEM: score against
+ * the items, ALS_USER: against the users), with an optional exclusion list per query: recommendations for a
+ * folded-in row without what it already has, for an average of rows, or for an item's own factor against
+ * the item side.  q is [n_q][rank], row-major.
+ *   Listed rows   for query i, the rows of dst_side whose raw id is not in
+ *                 excl_ids[excl_ptr[i] .. excl_ptr[i+1]).  excl_ptr == NULL: no exclusions.  The ids may come
+ *                 in any order, may repeat, and may name ids the model does not know (ignored); the result
+ *                 does not depend on their order.
+ *   Scoring       the F2J sdot of q[i] and the row's factor as als_get_factors returns it: fp32, strictly
+ *                 left to right over the rank, multiply and add rounded separately (no FMA), the sum
+ *                 starting from +0.0.
+ *   Selection     the best k in (score desc, id asc) order, the total order of als_recommend; -0.0 and +0.0
+ *                 tie.  A row whose score is NaN is never listed; +inf and -inf order normally.
+ *   Output        dst_ids_out / scores_out [n_q][k], dense; a list shorter than k is padded with id -1 and
+ *                 score NaN (the NaN tells the padding: -1 is a valid raw id).
+ * Two calls give identical bits; no floating-point atomics are used.
+ * Limits: 1 <= k <= 64, world = 1, n_q < 2^31: ALS_E_UNSUPPORTED beyond them (als_recommend serves larger k
+ * for rows the model holds).  Cosine similarity is not offered: normalise the vectors and the factors first.
+ * Errors: ALS_E_INVALID_ARGUMENT for a bad side, k < 1, a negative n_q, null q or outputs with n_q > 0, an
+ * excl_ptr that is negative or does not ascend, a null excl_ids with a non-empty range, more than 2^31 - 1
+ * exclusions; ALS_E_STATE when dst_side has no factors.  n_q = 0 is ALS_OK.
+ * The model is read-only: factors, bases, Gram caches, als_topk_stats, als_topk_timing,
+ * als_topk_last_rescan, sweep timings and path stats are unchanged, and a call between two half-sweeps
+ * leaves the fit bit-identical.  Contexts from als_model_create and forks may call it.
+ * ALBEDO_QUERY_SLICE_ROWS in the environment overrides the number of dst rows per scan slice (default: from
+ * the CU count). */
+int als_recommend_vectors(als_ctx* ctx, int dst_side, int32_t k,
+                          int64_t n_q, const float* q /* [n_q][rank] */,
+                          const int64_t* excl_ptr /* [n_q+1] or NULL */, const int32_t* excl_ids /* raw dst ids */,
+                          int32_t* dst_ids_out /* [n_q][k] */, float* scores_out /* [n_q][k] */);
+/* Device time of the last als_recommend_vectors call from HIP events on the context's stream (ms):
+ * out[0] = exclusion map + sort (0 without exclusions), out[1] = scan, out[2] = merge, out[3] = total. */
+int als_recommend_vectors_timing(const als_ctx* ctx, double* out4);
+
 /* ---- observability ---------------------------------------------------------------------------- */
 /* Per-stage device time (ms) of the last half-sweeps: see ALS_T_* indices. n = array length. */
 enum {
