@@ -41,6 +41,15 @@ def _launch(mode, out, world=2, timeout=300, env_extra=None, k=16):
     return np.load(out)
 
 
+def _assert_ranks_hold_the_same_factors(out, res, world):
+    """Every rank's own copy of both factor matrices (tests/mp_worker.py saves one file per rank) has the
+    bits of rank 0's."""
+    for r in range(world):
+        with np.load(out + f".factors.rank{r}.npz") as f:
+            for name in ("U", "V"):
+                assert np.array_equal(f[name].view(np.uint32), res[name].view(np.uint32)), (name, r)
+
+
 def _problem(k=16):
     from albedo_amd.synthetic import SynthSpec, generate
     d = generate(SynthSpec(1200, 400, 16000, seed=41))
@@ -100,6 +109,7 @@ def test_sharded_fit_gpu_matches_single(gpu_lib, tmp_path, world, nonneg, split,
     if k == 128:  # every light bucket and the wave kernel have rows
         deg = np.r_[np.diff(B.i_ptr), np.diff(B.u_ptr)]
         assert all(np.any((deg > lo) & (deg <= hi)) for lo, hi in ((0, 8), (8, 16), (16, 32), (32, 64), (64, 128)))
+    _assert_ranks_hold_the_same_factors(out, res, world)
     U, V = _fit_ref(B, U0, V0, k, 3, nonneg)
     rel = lambda a, b: np.max(np.abs(a - b)) / np.max(np.abs(b))
     assert rel(res["U"], U) < 1e-3 and rel(res["V"], V) < 1e-3
@@ -143,6 +153,7 @@ def test_sharded_sweep_gpu_c4_shaped(gpu_lib, tmp_path):
     rng = np.random.default_rng(3)
     U0 = rng.standard_normal((len(B.user_ids), k)).astype(np.float32)
     res = _launch("gpubig", str(tmp_path / "big.npz"), world=world, k=k, timeout=600)
+    _assert_ranks_hold_the_same_factors(str(tmp_path / "big.npz"), res, world)
     V_ref = cbind.half_sweep(U0, B.i_ptr, B.i_col, B.i_val, reg=0.5, alpha=40.0)
     U_ref = cbind.half_sweep(res["V"], B.u_ptr, B.u_col, B.u_val, reg=0.5, alpha=40.0)
     from tests.ladder import padded_rank, path_of, split_chunk
