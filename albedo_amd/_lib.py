@@ -71,7 +71,7 @@ class als_fold_params(C.Structure):
         ("reg_param", C.c_double),
         ("alpha", C.c_double),
         ("implicit_prefs", C.c_int32),
-        ("reserved", C.c_int32),
+        ("nonnegative", C.c_int32),
     ]
 
 
@@ -133,6 +133,7 @@ SIGNATURES = [
     ("als_fold_in", C.c_int, [P, C.c_int, C.POINTER(als_fold_params), C.c_int64, I32P, I32P, F32P, C.c_int64, I64P, I32P,
                               I64P, F32P]),
     ("als_fold_in_timing", C.c_int, [P, F64P]),
+    ("als_fold_in_stats", C.c_int, [P, I64P]),
     ("als_recommend_vectors", C.c_int, [P, C.c_int, C.c_int32, C.c_int64, F32P, I64P, I32P, I32P, F32P]),
     ("als_recommend_vectors_timing", C.c_int, [P, F64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
@@ -206,10 +207,12 @@ def device_count() -> int:
 
 
 
-def fold_in(ctx, side, row_id, src_id, rating, rank, reg_param=None, alpha=None, implicit_prefs=None, cap=None):
+def fold_in(ctx, side, row_id, src_id, rating, rank, reg_param=None, alpha=None, implicit_prefs=None, cap=None,
+            nonnegative=None):
     """als_fold_in on the context handle `ctx`: (ids ascending, degrees, factors [n_rows][rank]) of the distinct
     row ids.  The three parameters go together: all None means the context's own (fp = NULL).  cap: an upper
-    bound of the number of distinct row ids the caller knows (default: they are counted here)."""
+    bound of the number of distinct row ids the caller knows (default: they are counted here).  nonnegative
+    (with the three parameters): solve each row by Spark's NNLS in place of the Cholesky; None is False."""
     import numpy as np
 
     row_id = np.ascontiguousarray(row_id, dtype=np.int32)
@@ -223,7 +226,9 @@ def fold_in(ctx, side, row_id, src_id, rating, rank, reg_param=None, alpha=None,
     if any(given):
         if not all(given):
             raise ValueError("reg_param, alpha and implicit_prefs are given together or not at all")
-        fp = C.byref(als_fold_params(float(reg_param), float(alpha), int(bool(implicit_prefs)), 0))
+        fp = C.byref(als_fold_params(float(reg_param), float(alpha), int(bool(implicit_prefs)), int(bool(nonnegative))))
+    elif nonnegative is not None:
+        raise ValueError("nonnegative goes with reg_param, alpha and implicit_prefs (als_fold_params)")
     cap = int(np.unique(row_id).size) if cap is None else int(cap)
     ids = np.empty(cap, dtype=np.int32)
     deg = np.empty(cap, dtype=np.int64)
@@ -242,6 +247,16 @@ def fold_in_timing(ctx):
 
     out = np.zeros(4, dtype=np.float64)
     check(load().als_fold_in_timing(ctx, ptr(out, C.c_double)))
+    return out
+
+
+def fold_in_stats(ctx):
+    """als_fold_in_stats: NNLS iterations of the last call: [sum over rows, maximum, rows solved by NNLS, rows at
+    the iteration limit]; zeros after a Cholesky fold-in."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.int64)
+    check(load().als_fold_in_stats(ctx, ptr(out, C.c_int64)))
     return out
 
 

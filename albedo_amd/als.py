@@ -554,14 +554,16 @@ class ALSModel(_Params):
         return (out, eta) if per_row else out
 
     # ---- fold-in: factors for rows the fit did not see (als_fold_in) ---------------------------------
-    def _fold_params(self, regParam, alpha, implicitPrefs):
+    def _fold_params(self, regParam, alpha, implicitPrefs, nonnegative=None):
         vals = dict(regParam=regParam, alpha=alpha, implicitPrefs=implicitPrefs)
         for k, v in vals.items():
             if v is None:
                 if self._loaded:  # Spark's saved ALSModel carries the rank and the column names only
                     raise ValueError(f"foldIn on a loaded ALSModel needs {k}: the saved model does not carry it")
                 vals[k] = self._p[k]
-        return float(vals["regParam"]), float(vals["alpha"]), bool(vals["implicitPrefs"])
+        if nonnegative is None:  # a loaded model does not know how it was fitted: Cholesky unless told
+            nonnegative = False if self._loaded else self._p["nonnegative"]
+        return float(vals["regParam"]), float(vals["alpha"]), bool(vals["implicitPrefs"]), bool(nonnegative)
 
     @staticmethod
     def _side(side):
@@ -571,26 +573,29 @@ class ALSModel(_Params):
             return _lib.ALS_ITEM
         raise ValueError(f"side should be 'user' or 'item', not {side!r}")
 
-    def fold_in_np(self, rows, srcs, ratings, side="user", regParam=None, alpha=None, implicitPrefs=None):
+    def fold_in_np(self, rows, srcs, ratings, side="user", regParam=None, alpha=None, implicitPrefs=None,
+                   nonnegative=None):
         """(ids ascending, degrees, factors [n, rank]) of the distinct ids of `rows`, each solved from its
         (row, src, rating) triples against the model's frozen factors of the other side (als_fold_in).
-        Triples with a src id the model does not know are dropped; a row left with none gets zeros."""
+        Triples with a src id the model does not know are dropped; a row left with none gets zeros.
+        nonnegative: each row by Spark's NNLS, as ALS(nonnegative=True) computes it, in place of the Cholesky."""
         t = self._side(side)
         cols = (self._p["userCol"], self._p["itemCol"])
-        reg, al, imp = self._fold_params(regParam, alpha, implicitPrefs)
+        reg, al, imp, nn = self._fold_params(regParam, alpha, implicitPrefs, nonnegative)
         r = np.ascontiguousarray(_checked_cast(rows, cols[t]))
         s = np.ascontiguousarray(_checked_cast(srcs, cols[1 - t]))
-        return _lib.fold_in(self._h, t, r, s, np.ascontiguousarray(ratings, dtype=np.float32), self.rank, reg, al, imp)
+        return _lib.fold_in(self._h, t, r, s, np.ascontiguousarray(ratings, dtype=np.float32), self.rank, reg, al, imp,
+                            nonnegative=nn)
 
-    def foldIn(self, dataset, side="user", regParam=None, alpha=None, implicitPrefs=None):
+    def foldIn(self, dataset, side="user", regParam=None, alpha=None, implicitPrefs=None, nonnegative=None):
         """Factors of new users (side="user") or items from their ratings, as a frame of (id, features)
-        shaped like userFactors.  A model of ALS.fit defaults regParam, alpha and implicitPrefs to its own;
-        a loaded model needs all three."""
+        shaped like userFactors.  A model of ALS.fit defaults regParam, alpha, implicitPrefs and nonnegative to
+        its own; a loaded model needs the first three, and solves by Cholesky unless nonnegative=True."""
         t = self._side(side)
-        self._fold_params(regParam, alpha, implicitPrefs)  # a missing parameter is named before a missing column
+        self._fold_params(regParam, alpha, implicitPrefs, nonnegative)  # a missing parameter is named before a missing column
         cols = (self._p["userCol"], self._p["itemCol"])
         ids, _, f = self.fold_in_np(_column(dataset, cols[t]), _column(dataset, cols[1 - t]),
-                                    _column(dataset, self._p["ratingCol"]), t, regParam, alpha, implicitPrefs)
+                                    _column(dataset, self._p["ratingCol"]), t, regParam, alpha, implicitPrefs, nonnegative)
         return self._frame(ids, f)
 
     def _exclusions(self, ids, users, items):
@@ -636,7 +641,7 @@ class ALSModel(_Params):
         `dataset` (foldIn's keywords apply), then scored against the model's items on the model's own
         context (als_recommend_vectors).  excludeKnown: a user's lists leave out their items in `dataset`.
         numItems > 64 is served by als_recommend on a transient context, without excludeKnown."""
-        self._fold_params(*(fold_kw.get(k) for k in ("regParam", "alpha", "implicitPrefs")))
+        self._fold_params(*(fold_kw.get(k) for k in ("regParam", "alpha", "implicitPrefs", "nonnegative")))
         users, items = _column(dataset, self._p["userCol"]), _column(dataset, self._p["itemCol"])
         ids, _, f = self.fold_in_np(users, items, _column(dataset, self._p["ratingCol"]), _lib.ALS_USER, **fold_kw)
         if int(numItems) > 64 and not excludeKnown:
@@ -666,6 +671,11 @@ class ALSModel(_Params):
     def fold_in_timing(self):
         """Device ms of the last fold-in: csr (map + sort + CSR), gram (0 when cached), solve, total."""
         return dict(zip(("csr", "gram", "solve", "total"), _lib.fold_in_timing(self._h).tolist()))
+
+    def fold_in_stats(self):
+        """NNLS iterations of the last fold-in: iterations (summed over rows), max_iterations, rows (solved by
+        NNLS), rows_at_limit; all 0 after a Cholesky fold-in."""
+        return dict(zip(("iterations", "max_iterations", "rows", "rows_at_limit"), _lib.fold_in_stats(self._h).tolist()))
 
     # ---- persistence (Spark 2.2 ALSModelWriter / ALSModelReader layout: albedo_amd/persistence.py) ----
     MODEL_PARAMS = ("userCol", "itemCol", "predictionCol", "coldStartStrategy")  # ALSModelParams

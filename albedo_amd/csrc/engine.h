@@ -223,6 +223,8 @@ struct als_ctx {
   double eval_ms[5] = {0, 0, 0, 0, 0};
   // device time of the last als_fold_in call (ms): map + sort + CSR, src Gram, solve, total
   double fold_ms[4] = {0, 0, 0, 0};
+  // NNLS iterations of the last als_fold_in call: sum, maximum, rows solved, rows at the limit (0 after Cholesky)
+  int64_t fold_stats[4] = {0, 0, 0, 0};
   // device time of the last als_recommend_vectors call (ms): exclusion map + sort, scan, merge, total
   double query_ms[4] = {0, 0, 0, 0};
   hipEvent_t evt[5] = {};

@@ -24,6 +24,9 @@
 //             once per column.  L z = b rides along with the columns; the back substitution reads the
 //             triangle, one column per step.
 //     A pivot <= 0 or NaN ends the row and leaves its index in *bad (integer atomicMin).
+//   fold_solve_kernel<.., NNLS = true>  the same build, then Spark 2.2.0's NNLS.solve (mllib/optimization/NNLS.scala,
+//     restated in oracle/spark_als.py:nnls) on the row's system in place of the factorisation: the owners leave A
+//     in the packed triangle (LDS at KP <= 128, the scratch slab at KP = 256) and fold_nnls iterates on it.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
@@ -96,14 +99,236 @@ __host__ __device__ constexpr size_t fold_front_bytes(int KP, bool tri_lds) {
   const size_t tile = (size_t)FOLD_TILE * KP * 4, tri = tri_lds ? (size_t)fold_tri(KP) * 8 : 0;
   return tile > tri ? tile : tri;
 }
-// + the right-hand side / solution, two column buffers, z, 1 / diag(L), and c, w and (r > 0) of the tile's ratings
-__host__ __device__ constexpr size_t fold_lds_bytes(int KP, bool tri_lds) {
-  return fold_front_bytes(KP, tri_lds) + (size_t)(5 * KP + 3 * FOLD_TILE) * 8;
+// doubles behind the right-hand side.  Cholesky: two column buffers, z and 1 / diag(L).  NNLS: x, res, grad, dir
+// and lastDir, then the partial products of the threads 1 .. KP / 64 - 1 of each row for two vectors
+__host__ __device__ constexpr int fold_work_doubles(int KP, bool nnls) {
+  return nnls ? (5 + 2 * (KP / 64 - 1)) * KP : 4 * KP;
+}
+constexpr int FOLD_NNLS_SCALARS = 32;  // per-wave partial sums [4][4], 8 broadcast doubles, 4 ints
+// + the right-hand side / solution, the solver's vectors, c, w and (r > 0) of the tile's ratings, and the NNLS
+// loop's partial sums and broadcast scalars
+__host__ __device__ constexpr size_t fold_lds_bytes(int KP, bool tri_lds, bool nnls = false) {
+  return fold_front_bytes(KP, tri_lds) +
+         (size_t)(KP + fold_work_doubles(KP, nnls) + 3 * FOLD_TILE + (nnls ? FOLD_NNLS_SCALARS : 0)) * 8;
 }
 
 __device__ inline int tri_at(int i, int m) { return i * (i + 1) / 2 + m; }  // m <= i
 
-template <int KP, int TS, bool TRI_LDS>
+// ---- Spark's NNLS.solve on the packed triangle ------------------------------------------------------------
+// Thread tid = p * KP + r is thread p of row r: NT / KP = KP / 64 threads a row, each with 64 columns.
+// out = the part of (A v)_r over the columns [64 p, 64 p + 64) ∩ [0, k), added in ascending column order with
+// a product and a sum per entry, as the oracle's loop does (no fma: at k <= 64 the sum is the oracle's to the
+// bit).  Lanes are consecutive rows: entry (r, c) of the triangle lies at T(r) + c for c <= r, where the
+// triangular numbers spread 32 consecutive rows over all the 8-byte banks, and at T(c) + r above the diagonal,
+// which is contiguous across the lanes.
+template <int KP, int NV>
+__device__ __forceinline__ void fold_symv(const double* A, const int k, const int r, const int p, const double* v0,
+                                          const double* v1, double& s0, double& s1) {
+#pragma clang fp contract(off)
+  s0 = 0.0;
+  s1 = 0.0;
+  if (r >= k) return;
+  const int c0 = 64 * p, c1 = k < c0 + 64 ? k : c0 + 64, tr = r * (r + 1) / 2;
+  int tc = c0 * (c0 + 1) / 2;  // T(c): p is the same in every lane of a wave, so c and T(c) stay scalar
+#pragma unroll 8
+  for (int c = c0; c < c1; ++c) {
+    const int below = tr + c, above = tc + r;  // both formed, one selected: no branch per entry
+    const double e = A[c <= r ? below : above];
+    s0 += e * v0[c];
+    if (NV == 2) s1 += e * v1[c];
+    tc += c + 1;
+  }
+}
+
+// Σ over the rows of N values at once: a butterfly inside each of the KP / 64 waves that hold the row threads
+// (every lane ends with the same bits: a + b = b + a), lane 0 leaves the wave's sums in wp[wave][4].  The caller's
+// barrier follows; thread 0 then adds the waves in ascending order.
+template <int KP, int N>
+__device__ __forceinline__ void fold_wave_sums(const int tid, double (&v)[N], double* wp) {
+  if (tid < KP) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+      for (int q = 0; q < N; ++q) v[q] += __shfl_xor(v[q], off);
+    if ((tid & 63) == 0)
+#pragma unroll
+      for (int q = 0; q < N; ++q) wp[(tid >> 6) * 4 + q] = v[q];
+  }
+}
+
+__device__ __forceinline__ double fold_add_waves(const double* wp, const int nw, const int q) {
+  double s = wp[q];
+  for (int w = 1; w < nw; ++w) s += wp[w * 4 + q];
+  return s;
+}
+
+__device__ __forceinline__ bool fold_nnls_stop(const double step, const double ndir, const double nx) {
+  return step != step || step < 1e-7 || step > 1e40 || ndir < 1e-12 * nx || ndir < 1e-32;
+}
+
+// NNLS.solve for the k x k system (A in the packed triangle, b) of one row: x0 = 0, at most max(400, 20 k)
+// iterations of: res = A x - b, the projected gradient, the steepest-descent step, the conjugate direction once
+// iterno > lastWall + 1, the stop test, the step clamp, the update with the wall rule.  Every sum has one fixed
+// order.  The scalars of an iteration (the norms, alpha, step, stop, which direction, whether a wall was hit)
+// are computed by thread 0 or set as a flag in LDS and read by every thread behind a barrier, so every thread
+// takes the same branches and leaves the loop in the same iteration.  Returns the iterations taken; x is left
+// in w[0 .. k).
+template <int KP, int NT>
+__device__ __forceinline__ int fold_nnls(const double* A, const int k, const int tid, const double* b, double* w,
+                                         double* wp) {
+#pragma clang fp contract(off)
+  constexpr int P = NT / KP, NW = KP / 64;
+  static_assert(P == NW && NW >= 1 && NW <= 4, "64 columns per thread of a row");
+  double *x = w, *res = x + KP, *grad = res + KP, *dir = grad + KP, *last = dir + KP;
+  double* pg = last + KP;           // [P - 1][KP] partial products with grad (or x)
+  double* pd = pg + (P - 1) * KP;   // [P - 1][KP] and with dir
+  double* sc = wp + 16;             // 0 ngrad, 1 grad·res, 2 ‖x‖², 3 alpha, 4 step
+  int* fl = reinterpret_cast<int*>(sc + 8);  // 0 stop, 1 dir = grad after all, 2 the clamp binds, 3 a wall was hit
+  // a wave holds 64 consecutive threads and KP is a multiple of 64: p is uniform in the wave, and kept scalar
+  const int r = tid % KP, p = __builtin_amdgcn_readfirstlane(tid) / KP;
+  const bool mine = p == 0 && r < k;  // this thread finishes row r
+  const int iter_max = 20 * k > 400 ? 20 * k : 400;
+  if (tid < KP) {
+    x[tid] = 0.0;
+    last[tid] = 0.0;
+  }
+  double last_norm = 0.0;
+  int iterno = 0, last_wall = 0;
+  __syncthreads();  // A, b and x = 0 are there
+  while (iterno < iter_max) {
+    double s0, s1;
+    fold_symv<KP, 1>(A, k, r, p, x, x, s0, s1);
+    if (P > 1) {
+      if (p > 0 && r < k) pg[(p - 1) * KP + r] = s0;
+      __syncthreads();
+    }
+    double g = 0.0, rs = 0.0, xi = 0.0;
+    if (mine) {
+      for (int q = 1; q < P; ++q) s0 += pg[(q - 1) * KP + r];
+      rs = s0 - b[r];
+      xi = x[r];
+      g = rs > 0.0 && xi == 0.0 ? 0.0 : rs;
+      res[r] = rs;
+      grad[r] = g;
+    }
+    double v3[3] = {g * g, g * rs, xi * xi};
+    fold_wave_sums<KP, 3>(tid, v3, wp);
+    __syncthreads();
+    const bool cg = iterno > last_wall + 1;
+    if (tid == 0) {
+      const double ngrad = fold_add_waves(wp, NW, 0);
+      sc[0] = ngrad;
+      sc[1] = fold_add_waves(wp, NW, 1);
+      sc[2] = fold_add_waves(wp, NW, 2);
+      sc[3] = ngrad / last_norm;  // read only when cg
+    }
+    __syncthreads();
+    const double ngrad = sc[0];
+    double d = g;
+    if (mine) {
+      if (cg) d = g + sc[3] * last[r];
+      dir[r] = d;
+    }
+    __syncthreads();
+    // A grad and A dir in one pass over the triangle
+    if (cg) fold_symv<KP, 2>(A, k, r, p, grad, dir, s0, s1);
+    else fold_symv<KP, 1>(A, k, r, p, grad, grad, s0, s1);
+    if (P > 1) {
+      if (p > 0 && r < k) {
+        pg[(p - 1) * KP + r] = s0;
+        pd[(p - 1) * KP + r] = s1;
+      }
+      __syncthreads();
+    }
+    double v4[4] = {0.0, 0.0, 0.0, 0.0};
+    if (mine) {
+      for (int q = 1; q < P; ++q) {
+        s0 += pg[(q - 1) * KP + r];
+        s1 += pd[(q - 1) * KP + r];
+      }
+      v4[0] = s0 * g;
+      if (cg) {
+        v4[1] = d * rs;
+        v4[2] = s1 * d;
+        v4[3] = d * d;
+      }
+    }
+    fold_wave_sums<KP, 4>(tid, v4, wp);
+    __syncthreads();
+    if (tid == 0) {
+      const double nx = sc[2];
+      double step = sc[1] / (fold_add_waves(wp, NW, 0) + 1e-20), ndir = ngrad;
+      int back = 0;
+      if (cg) {
+        const double dstep = fold_add_waves(wp, NW, 1) / (fold_add_waves(wp, NW, 2) + 1e-20);
+        const double nd = fold_add_waves(wp, NW, 3);
+        if (fold_nnls_stop(dstep, nd, nx)) {
+          back = 1;
+        } else {
+          step = dstep;
+          ndir = nd;
+        }
+      }
+      sc[4] = step;
+      fl[0] = fold_nnls_stop(step, ndir, nx);
+      fl[1] = back;
+      fl[2] = 0;
+      fl[3] = 0;
+    }
+    __syncthreads();
+    if (fl[0]) break;
+    double step = sc[4];
+    if (mine) {
+      if (fl[1]) {
+        d = g;
+        dir[r] = d;
+      }
+      if (step * d > xi) fl[2] = 1;
+    }
+    __syncthreads();
+    if (fl[2]) {
+      // The clamp binds somewhere.  Spark's loop `if (step * dir[i] > x[i]) step = x[i] / dir[i]` runs in index
+      // order with the step shrinking as it goes; wave 0 runs it 64 indices at a time: the first index whose
+      // test holds at the current step sets the step, and only the indices behind it are tested again.  The
+      // same products, comparisons and quotients in the same order as the serial loop.
+      if (tid < 64) {
+        double st = step;
+        for (int base = 0; base < k; base += 64) {
+          const int i = base + tid;
+          const double di = i < k ? dir[i] : 0.0, xv = i < k ? x[i] : 0.0;
+          const double q = xv / di;  // taken only where the test holds, which needs dir[i] > 0
+          unsigned long long todo = ~0ull;
+          for (;;) {
+            const unsigned long long m = __ballot(st * di > xv) & todo;
+            if (!m) break;
+            const int j = __ffsll(m) - 1;
+            st = __shfl(q, j);
+            todo = j == 63 ? 0ull : ~0ull << (j + 1);
+          }
+        }
+        if (tid == 0) sc[4] = st;
+      }
+      __syncthreads();
+      step = sc[4];
+    }
+    if (mine) {
+      if (step * d > xi * (1 - 1e-14)) {
+        x[r] = 0.0;
+        fl[3] = 1;
+      } else {
+        x[r] = xi - step * d;
+      }
+      last[r] = d;
+    }
+    __syncthreads();
+    if (fl[3]) last_wall = iterno;
+    ++iterno;
+    last_norm = ngrad;
+  }
+  return iterno;
+}
+
+template <int KP, int TS, bool TRI_LDS, bool NNLS>
 __global__ __launch_bounds__(TS* TS) void fold_solve_kernel(const FoldArgs a) {
   constexpr int NT = TS * TS, NB = KP / TS, Q = KP / 4;
   constexpr int PER = FOLD_TILE * Q / NT;  // 16-byte loads per thread and tile
@@ -111,10 +336,10 @@ __global__ __launch_bounds__(TS* TS) void fold_solve_kernel(const FoldArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* tile = reinterpret_cast<float*>(smem);  // [FOLD_TILE][KP]
   double* vec = reinterpret_cast<double*>(smem + fold_front_bytes(KP, TRI_LDS));  // b, then x
-  double* colb = vec + KP;                                                        // two column buffers
+  double* colb = vec + KP;                                                        // two column buffers (NNLS: fold_nnls's vectors)
   double* zb = colb + 2 * KP;
   double* dinv = zb + KP;
-  double* cw = dinv + KP;
+  double* cw = colb + fold_work_doubles(KP, NNLS);
   double* ww = cw + FOLD_TILE;
   double* pw = ww + FOLD_TILE;
   double* A = TRI_LDS ? reinterpret_cast<double*>(smem) : a.scratch + (size_t)blockIdx.x * fold_tri(KP);
@@ -198,6 +423,26 @@ __global__ __launch_bounds__(TS* TS) void fold_solve_kernel(const FoldArgs a) {
         if (i == m) acc[ia][ib] += ln;
       }
     if (tid < KP) vec[tid] = bacc;
+    if constexpr (NNLS) {
+      // ---- NNLS.solve on A: the owners leave their entries in the packed triangle ----
+      __syncthreads();  // the last tile is read, the triangle may take its place
+#pragma unroll
+      for (int ia = 0; ia < NB; ++ia)
+#pragma unroll
+        for (int ib = 0; ib <= ia; ++ib) {
+          const int i = ty + TS * ia, m = tx + TS * ib;
+          if (m <= i && i < k) A[tri_at(i, m)] = acc[ia][ib];
+        }
+      const int it = fold_nnls<KP, NT>(A, k, tid, vec, colb, pw + FOLD_TILE);
+      for (int i = tid; i < k; i += NT) xo[i] = (float)colb[i];
+      if (tid == 0) {  // integers: the order of arrival does not show
+        atomicAdd(a.stats, (unsigned long long)it);
+        atomicMax(a.stats + 1, (unsigned long long)it);
+        atomicAdd(a.stats + 2, 1ull);
+        if (it >= (20 * k > 400 ? 20 * k : 400)) atomicAdd(a.stats + 3, 1ull);
+      }
+      continue;
+    }
     // ---- A = L Lᵀ, right-looking, in the registers that built A ----
     // Column j: its owners (tx = j mod TS) put it into LDS, every thread reads the pivot and the entries of
     // its own rows and columns, and updates its part of the trailing triangle in registers; the owners leave
@@ -267,15 +512,15 @@ __global__ __launch_bounds__(TS* TS) void fold_solve_kernel(const FoldArgs a) {
   }
 }
 
-template <int KP, int TS, bool TRI_LDS>
+template <int KP, int TS, bool TRI_LDS, bool NNLS>
 hipError_t fold_launch(const FoldArgs& a, int n_wg, hipStream_t s) {
-  constexpr size_t lds = fold_lds_bytes(KP, TRI_LDS);
+  constexpr size_t lds = fold_lds_bytes(KP, TRI_LDS, NNLS);
   if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fold_solve_kernel<KP, TS, TRI_LDS>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fold_solve_kernel<KP, TS, TRI_LDS, NNLS>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  fold_solve_kernel<KP, TS, TRI_LDS><<<n_wg, TS * TS, lds, s>>>(a);
+  fold_solve_kernel<KP, TS, TRI_LDS, NNLS><<<n_wg, TS * TS, lds, s>>>(a);
   return hipGetLastError();
 }
 
@@ -327,7 +572,8 @@ hipError_t fold_build_csr(const int32_t* row_id, const int32_t* src_id, const fl
 }
 
 // KP = 64: one wave per row (its barriers cost nothing) and 19 KB of LDS, eight rows per CU; KP = 128: 69 KB
-// of LDS, two per CU; KP = 256: 1024 threads at the registers of the build, one per CU
+// of LDS, two per CU; KP = 256: 1024 threads at the registers of the build, one per CU.  The NNLS instances
+// take 20 KB, 74 KB and 57 KB: the same counts fit
 int fold_workgroups(int KP, int64_t n_rows, int n_cu) {
   int64_t wgs = (int64_t)n_cu * (KP == 64 ? 8 : KP == 128 ? 2 : 1);
   const char* e = std::getenv("ALBEDO_FOLD_WGS");
@@ -340,9 +586,17 @@ size_t fold_scratch_doubles(int KP, int n_wg) { return KP == 256 ? (size_t)n_wg 
 hipError_t launch_fold_solve(int KP, const FoldArgs& a, int n_wg, hipStream_t s) {
   if (a.n_rows <= 0) return hipSuccess;
   if (n_wg <= 0 || a.k <= 0 || a.k > KP || a.n_rows > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
-  if (KP == 64) return fold_launch<64, 8, true>(a, n_wg, s);
-  if (KP == 128) return fold_launch<128, 16, true>(a, n_wg, s);
-  if (KP == 256) return a.scratch ? fold_launch<256, 32, false>(a, n_wg, s) : hipErrorInvalidValue;
+  if (KP == 256 && !a.scratch) return hipErrorInvalidValue;
+  if (a.nonnegative) {
+    if (!a.stats) return hipErrorInvalidValue;
+    if (KP == 64) return fold_launch<64, 8, true, true>(a, n_wg, s);
+    if (KP == 128) return fold_launch<128, 16, true, true>(a, n_wg, s);
+    if (KP == 256) return fold_launch<256, 32, false, true>(a, n_wg, s);
+    return hipErrorInvalidValue;
+  }
+  if (KP == 64) return fold_launch<64, 8, true, false>(a, n_wg, s);
+  if (KP == 128) return fold_launch<128, 16, true, false>(a, n_wg, s);
+  if (KP == 256) return fold_launch<256, 32, false, false>(a, n_wg, s);
   return hipErrorInvalidValue;
 }
 

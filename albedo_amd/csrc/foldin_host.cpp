@@ -1,6 +1,7 @@
 // als_fold_in: host side of the fold-in (foldin.hip).  The call brings the src side's factors into the
 // original basis, takes the fp64 src Gram from the side's fold-in cache (or forms it there), turns the
-// triples into a CSR on the device and solves every distinct row.  It reads the model and writes nothing
+// triples into a CSR on the device and solves every distinct row, by Cholesky or (als_fold_params.nonnegative)
+// by Spark's NNLS.solve.  It reads the model and writes nothing
 // of it: no factor, basis, Gram, timing or path counter of a half-sweep changes.  Every buffer but the
 // cached Gram (Side::d_foldG) is owned by the call.
 #include <hip/hip_runtime.h>
@@ -45,7 +46,7 @@ struct Marks {  // stage marks on the stream
   }
 };
 
-int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_t n, const int32_t* row_id,
+int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int nonneg, int64_t n, const int32_t* row_id,
             const int32_t* src_id, const float* rating, int64_t cap, int64_t* n_rows_out, int32_t* ids_out,
             int64_t* degree_out, float* factors_out) {
   Side& S = c->s[1 - side];
@@ -53,7 +54,7 @@ int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   hipStream_t st = c->st;
   TRYC(materialize(c, 1 - side));
   DevBuf d_row, d_src, d_val, d_sids, d_key, d_keys, d_vals, d_hi, d_col, d_runs, d_cnt, d_ptr, d_nr, d_ids, d_deg, d_degs;
-  DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad, d_X;
+  DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad, d_stats, d_X;
   Marks clk;
   Drain queued{st};
   for (DevBuf* b : {&d_row, &d_src, &d_val, &d_vals, &d_hi, &d_col, &d_runs, &d_ids, &d_deg, &d_degs, &d_iota, &d_order})
@@ -64,6 +65,7 @@ int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   HIPCHK(d_ptr.ensure((size_t)(n + 1) * 8));
   HIPCHK(d_nr.ensure(8));
   HIPCHK(d_bad.ensure(4));
+  HIPCHK(d_stats.ensure(4 * 8));
   HIPCHK(d_sids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));
   const size_t tb = fold_sort_temp_bytes(n);
   HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
@@ -73,6 +75,7 @@ int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   HIPCHK(hipMemcpyAsync(d_sids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
   const int bad0 = INT_MAX;
   HIPCHK(hipMemcpyAsync(d_bad.p, &bad0, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d_stats.p, 0, 4 * 8, st));
   HIPCHK(clk.mark(0, st));
   FoldCsr f{};
   f.key = d_key.as<uint64_t>();
@@ -121,11 +124,16 @@ int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   a.scratch = sd ? d_scratch.as<double>() : nullptr;
   a.bad = d_bad.as<int>();
   a.X = d_X.as<float>();
+  a.nonnegative = nonneg;
+  a.stats = d_stats.as<unsigned long long>();
   HIPCHK(launch_fold_solve(KP, a, n_wg, st));
   HIPCHK(clk.mark(3, st));
   int bad = INT_MAX;
+  unsigned long long stats[4] = {0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(stats, d_stats.p, sizeof stats, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < 4; ++i) c->fold_stats[i] = (int64_t)stats[i];
   if (form_gram) S.fold_gram_valid = true;
   c->fold_ms[0] = event_ms(clk.e[0], clk.e[1]);
   c->fold_ms[1] = form_gram ? event_ms(clk.e[1], clk.e[2]) : 0.0;
@@ -164,11 +172,14 @@ extern "C" int als_fold_in(als_ctx* c, int side, const als_fold_params* fp, int6
   if (!fp && c->model_only)
     return fail(ALS_E_INVALID_ARGUMENT,
                 "als_fold_in: a model-only context has no regParam, alpha or implicitPrefs: pass als_fold_params");
-  if (c->p.nonnegative) return fail(ALS_E_UNSUPPORTED, "als_fold_in does not support nonnegative = true (NNLS)");
+  if (!fp && c->p.nonnegative)
+    return fail(ALS_E_UNSUPPORTED,
+                "als_fold_in without als_fold_params does not solve by NNLS: pass als_fold_params with nonnegative = 1");
   if (c->world > 1) return fail(ALS_E_UNSUPPORTED, "als_fold_in is single-process (world = 1)");
   if (n > (int64_t)0x7FFFFFFF) return fail(ALS_E_UNSUPPORTED, "als_fold_in takes at most 2^31 - 1 triples a call");
   *n_rows_out = 0;
   for (double& v : c->fold_ms) v = 0.0;
+  for (int64_t& v : c->fold_stats) v = 0;
   if (n == 0) return ALS_OK;
   if (!c->s[1 - side].has_factors)
     return fail(ALS_E_STATE, std::string("als_fold_in needs the ") + (side == ALS_USER ? "item" : "user") +
@@ -176,8 +187,15 @@ extern "C" int als_fold_in(als_ctx* c, int side, const als_fold_params* fp, int6
   TRYC(set_device(c));
   const double reg = fp ? fp->reg_param : c->p.reg_param, alpha = fp ? fp->alpha : c->p.alpha;
   const int implicit = fp ? fp->implicit_prefs != 0 : c->p.implicit_prefs != 0;
-  return fold_in(c, side, reg, alpha, implicit, n, row_id, src_id, rating, cap, n_rows_out, ids_out, degree_out,
+  const int nonneg = fp ? fp->nonnegative != 0 : 0;  // fp == NULL on a nonnegative context was refused above
+  return fold_in(c, side, reg, alpha, implicit, nonneg, n, row_id, src_id, rating, cap, n_rows_out, ids_out, degree_out,
                  factors_out);
+}
+
+extern "C" int als_fold_in_stats(const als_ctx* c, int64_t* out4) {
+  if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  for (int i = 0; i < 4; ++i) out4[i] = c->fold_stats[i];
+  return ALS_OK;
 }
 
 extern "C" int als_fold_in_timing(const als_ctx* c, double* out4) {

@@ -363,6 +363,9 @@ struct FoldArgs {
   double* scratch;        // KP = 256: fold_scratch_doubles of packed triangles, one per workgroup
   int* bad;               // atomicMin of the rows that met a pivot <= 0 or NaN (caller sets it to INT_MAX)
   float* X;               // out [n_rows][k], row order (degree-0 rows: zeros)
+  int nonnegative;        // Spark's NNLS.solve in place of the Cholesky factorisation
+  unsigned long long* stats;  // nonnegative: [4] NNLS iterations summed and their maximum, rows solved, rows at
+                              // the iteration limit (integer atomics; the caller clears them)
 };
 int fold_workgroups(int KP, int64_t n_rows, int n_cu);  // the persistent grid (ALBEDO_FOLD_WGS caps it)
 size_t fold_scratch_doubles(int KP, int n_wg);

@@ -214,7 +214,7 @@ int als_predict(als_ctx* ctx, int64_t n, const int32_t* user, const int32_t* ite
 /* ---- fold-in: factors for rows the fit did not see ---------------------------------------------- */
 typedef struct als_fold_params {   /* the normal equation's parameters, as als_params */
   double reg_param, alpha;
-  int32_t implicit_prefs, reserved;   /* reserved = 0 */
+  int32_t implicit_prefs, nonnegative;   /* nonnegative != 0: solve by NNLS (0, the former reserved field: Cholesky) */
 } als_fold_params;
 /* The factors of new rows of `side` from their (row_id, src_id, rating) triples, each row solved against
  * the current factors of the other side, which stay frozen ("recalculate user"): side = ALS_USER gives new
@@ -224,6 +224,11 @@ typedef struct als_fold_params {   /* the normal equation's parameters, as als_p
  *   (G + sum_i c_i y_i y_i^T + regParam·n_j·I) x_j = sum_i w_i y_i
  * built and solved by Cholesky in fp64, in the original basis (the src factors are what als_get_factors
  * returns), at the model rank, and rounded to fp32.
+ * With fp->nonnegative != 0 the same system, as the full symmetric matrix with regParam·n_j on its diagonal, goes
+ * through Spark 2.2.0's NNLSSolver instead (mllib/optimization/NNLS.scala solve, in fp64: x0 = 0, at most
+ * max(400, 20·rank) iterations, its stop rules included), and x is rounded once to fp32: the row that
+ * ALS.setNonnegative(true) would compute.  NNLS has no "not positive definite" outcome: a singular system is
+ * ALS_OK with whatever the loop returns.
  * The model is read-only: the context's factors, bases, Gram state, timings and path stats are unchanged,
  * and a fold-in between two half-sweeps leaves the fit bit-identical.  row_id is any int32; it may
  * coincide with an id the model already has on that side: the call then recomputes that row and stores
@@ -236,23 +241,31 @@ typedef struct als_fold_params {   /* the normal equation's parameters, as als_p
  * (except among copies of one pair with different ratings); no floating-point atomics are used and two
  * calls give identical bits.
  * fp == NULL means the context's own regParam, alpha and implicitPrefs.  A context from als_model_create
- * has none (Spark's saved ALSModel carries only the rank) and requires fp.
- * Errors: ALS_E_UNSUPPORTED for a context with nonnegative = true (NNLS fold-in is not implemented), for
+ * has none (Spark's saved ALSModel carries only the rank) and requires fp.  When fp is given, fp alone decides
+ * the solver, on a context created with nonnegative = true too; fp == NULL does not take the context's
+ * nonnegative: in ABI version 1 it stays ALS_E_UNSUPPORTED on such a context (pass fp with nonnegative = 1).
+ * Errors: ALS_E_UNSUPPORTED for fp == NULL on a context with nonnegative = true, for
  * world > 1 and for n >= 2^31; ALS_E_STATE when the src side has no factors; ALS_E_INVALID_ARGUMENT for
  * a bad side, a negative n, a NaN or negative reg_param / alpha, null inputs with n > 0, a null
  * n_rows_out, and fp == NULL on a model-only context.  n = 0 is ALS_OK with *n_rows_out = 0.  Forks may
- * call it.  A pivot <= 0 or NaN (regParam·n = 0 on a singular system) fails the call with
+ * call it.  In the Cholesky solve a pivot <= 0 or NaN (regParam·n = 0 on a singular system) fails the call with
  * ALS_E_NOT_POSITIVE_DEFINITE; the message names the lowest failing raw id, and the outputs are then
  * unspecified.  The fp64 src Gram is kept per side until that side's factors change, so further calls
- * (one user at a time on a serving context) skip it.  ALBEDO_FOLD_WGS in the environment caps the
- * persistent grid of the solve (one workgroup per row). */
+ * (one user at a time on a serving context) skip it; the Cholesky and the NNLS fold-in share it.
+ * ALBEDO_FOLD_WGS in the environment caps the persistent grid of the solve (one workgroup per row); the
+ * result does not depend on it. */
 int als_fold_in(als_ctx* ctx, int side, const als_fold_params* fp,
                 int64_t n, const int32_t* row_id, const int32_t* src_id, const float* rating,
                 int64_t cap, int64_t* n_rows_out, int32_t* ids_out, int64_t* degree_out,
                 float* factors_out /* [cap][rank] */);
 /* Device time of the last als_fold_in call from HIP events on the context's stream (ms): out[0] = id
- * mapping + sort + CSR, out[1] = src Gram (0 when taken from the cache), out[2] = solve, out[3] = total. */
+ * mapping + sort + CSR, out[1] = src Gram (0 when taken from the cache), out[2] = solve (whichever solver
+ * ran), out[3] = total. */
 int als_fold_in_timing(const als_ctx* ctx, double* out4);
+/* NNLS iterations of the last als_fold_in call: out[0] = summed over rows, out[1] = the maximum over rows,
+ * out[2] = rows solved by NNLS (those with a surviving triple), out[3] = rows that ran into the iteration
+ * limit max(400, 20·rank).  All four are 0 after a Cholesky call. */
+int als_fold_in_stats(const als_ctx* ctx, int64_t* out4);
 
 /* Exact top-k of caller-supplied query vectors against the factors of `dst_side` (ALS_ITEM: score against
  * the items, ALS_USER: against the users), with an optional exclusion list per query: recommendations for a
