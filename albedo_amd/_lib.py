@@ -134,6 +134,9 @@ SIGNATURES = [
                               I64P, F32P]),
     ("als_fold_in_timing", C.c_int, [P, F64P]),
     ("als_fold_in_stats", C.c_int, [P, I64P]),
+    ("als_explain", C.c_int, [P, C.c_int, C.POINTER(als_fold_params), C.c_int64, I32P, I32P, F32P, C.c_int64, I32P, I32P,
+                              C.c_int32, F64P, I32P, F64P]),
+    ("als_explain_timing", C.c_int, [P, F64P]),
     ("als_recommend_vectors", C.c_int, [P, C.c_int, C.c_int32, C.c_int64, F32P, I64P, I32P, I32P, F32P]),
     ("als_recommend_vectors_timing", C.c_int, [P, F64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
@@ -257,6 +260,47 @@ def fold_in_stats(ctx):
 
     out = np.zeros(4, dtype=np.int64)
     check(load().als_fold_in_stats(ctx, ptr(out, C.c_int64)))
+    return out
+
+
+def explain(ctx, side, row_id, src_id, rating, pair_row_id, pair_target_id, m, reg_param=None, alpha=None,
+            implicit_prefs=None):
+    """als_explain on the context handle `ctx`: (totals [n_pairs], src ids [n_pairs, m], contributions
+    [n_pairs, m]) of the pairs (row, target of the src side) over the rows the triples describe, -1 / NaN padded.
+    The three parameters go together, as in fold_in: all None means the context's own (fp = NULL)."""
+    import numpy as np
+
+    row_id = np.ascontiguousarray(row_id, dtype=np.int32)
+    src_id = np.ascontiguousarray(src_id, dtype=np.int32)
+    rating = np.ascontiguousarray(rating, dtype=np.float32)
+    pair_row_id = np.ascontiguousarray(pair_row_id, dtype=np.int32)
+    pair_target_id = np.ascontiguousarray(pair_target_id, dtype=np.int32)
+    n, n_pairs, m = int(row_id.shape[0]), int(pair_row_id.shape[0]), int(m)
+    if row_id.ndim != 1 or src_id.shape != (n,) or rating.shape != (n,):
+        raise ValueError("row_id, src_id and rating should be one-dimensional and of one length")
+    if pair_row_id.ndim != 1 or pair_target_id.shape != (n_pairs,):
+        raise ValueError("pair_row_id and pair_target_id should be one-dimensional and of one length")
+    given = [v is not None for v in (reg_param, alpha, implicit_prefs)]
+    fp = None
+    if any(given):
+        if not all(given):
+            raise ValueError("reg_param, alpha and implicit_prefs are given together or not at all")
+        fp = C.byref(als_fold_params(float(reg_param), float(alpha), int(bool(implicit_prefs)), 0))
+    total = np.empty(n_pairs, dtype=np.float64)
+    ids = np.empty((n_pairs, max(m, 0)), dtype=np.int32)
+    contrib = np.empty((n_pairs, max(m, 0)), dtype=np.float64)
+    check(load().als_explain(ctx, side, fp, n, ptr(row_id, C.c_int32), ptr(src_id, C.c_int32), ptr(rating, C.c_float),
+                             n_pairs, ptr(pair_row_id, C.c_int32), ptr(pair_target_id, C.c_int32), m,
+                             ptr(total, C.c_double), ptr(ids, C.c_int32), ptr(contrib, C.c_double)))
+    return total, ids, contrib
+
+
+def explain_timing(ctx):
+    """als_explain_timing: device ms of the last call: [map + sort + CSR, src Gram, solve + select, total]."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.float64)
+    check(load().als_explain_timing(ctx, ptr(out, C.c_double)))
     return out
 
 

@@ -636,19 +636,113 @@ class ALSModel(_Params):
         """Device ms of the last recommend_vectors_np: exclusions (map + sort), scan, merge, total."""
         return dict(zip(("exclusions", "scan", "merge", "total"), _lib.recommend_vectors_timing(self._h).tolist()))
 
-    def recommendForNewUsers(self, dataset, numItems, excludeKnown=False, **fold_kw):
+    def recommendForNewUsers(self, dataset, numItems, excludeKnown=False, explain=None, **fold_kw):
         """recommendForUserSubset for users the model has not seen: their factors are folded in from
         `dataset` (foldIn's keywords apply), then scored against the model's items on the model's own
         context (als_recommend_vectors).  excludeKnown: a user's lists leave out their items in `dataset`.
-        numItems > 64 is served by als_recommend on a transient context, without excludeKnown."""
+        numItems > 64 is served by als_recommend on a transient context, without excludeKnown.
+        explain=m adds an `explanation` column: for every listed item a dict of the item, its `score` in fp64
+        before the factor was rounded (als_explain's total) and its `explanation`, the m ratings of the user
+        that contribute most, as (item id, contribution)."""
         self._fold_params(*(fold_kw.get(k) for k in ("regParam", "alpha", "implicitPrefs", "nonnegative")))
         users, items = _column(dataset, self._p["userCol"]), _column(dataset, self._p["itemCol"])
-        ids, _, f = self.fold_in_np(users, items, _column(dataset, self._p["ratingCol"]), _lib.ALS_USER, **fold_kw)
+        ratings = _column(dataset, self._p["ratingCol"])
+        ids, _, f = self.fold_in_np(users, items, ratings, _lib.ALS_USER, **fold_kw)
         if int(numItems) > 64 and not excludeKnown:
+            if explain is not None:
+                raise ValueError("explain goes with numItems <= 64")
             return self._recommend_transient(ids, f, numItems)
         excl = self._exclusions(ids, users, items) if excludeKnown else None
         dst, sc = self.recommend_vectors_np(f, numItems, excl, "item")
-        return self._rec_frame(ids, dst, sc, self._p["userCol"], self._p["itemCol"])
+        out = self._rec_frame(ids, dst, sc, self._p["userCol"], self._p["itemCol"])
+        if explain is None:
+            return out
+        fold_kw.pop("nonnegative", None)  # resolved above: explain_np refuses an NNLS model itself
+        listed = ~np.isnan(sc)
+        pu, pt = np.repeat(ids, listed.sum(axis=1)), dst[listed]
+        total, eids, ev = self.explain_np(users, items, ratings, pu, pt, explain, "user", **fold_kw)
+        by_user, at = {}, 0
+        for r in range(len(ids)):
+            n = int(listed[r].sum())
+            if n:
+                by_user[int(ids[r])] = [
+                    {self._p["itemCol"]: int(pt[p]), "score": float(total[p]),
+                     "explanation": self._explanation(eids[p], ev[p])} for p in range(at, at + n)]
+            at += n
+        out["explanation"] = [by_user[int(u)] for u in out[self._p["userCol"]]]
+        return out
+
+    # ---- explanations: each rating's share of a score (als_explain) ----------------------------------
+    @staticmethod
+    def _explanation(ids, values):
+        m = ~np.isnan(values)  # the NaN tells the padding: -1 is a valid raw id
+        return [(int(i), float(v)) for i, v in zip(ids[m], values[m])]
+
+    def explain_np(self, rows, srcs, ratings, pair_rows, pair_targets, num=10, side="user", regParam=None, alpha=None,
+                   implicitPrefs=None):
+        """(total [n_pairs], src ids [n_pairs, num], contributions [n_pairs, num]) of als_explain: for each pair
+        (row, target) the share of the row's score for the target that each of the row's ratings contributes,
+        the `num` largest by (value desc, id asc) with -1 / NaN padding, and their sum over all the row's
+        ratings.  The rows are given by their (row, src, rating) triples as for fold_in_np; with side="user" the
+        targets are items.  A model fitted with nonnegative=True has no such decomposition: an NNLS row is not
+        linear in its ratings."""
+        t = self._side(side)
+        cols = (self._p["userCol"], self._p["itemCol"])
+        reg, al, imp, nn = self._fold_params(regParam, alpha, implicitPrefs)
+        if nn:
+            raise ValueError("explain: an NNLS row is not linear in its ratings, so this decomposition is not its "
+                             "score (the model was fitted with nonnegative=True)")
+        r = np.ascontiguousarray(_checked_cast(rows, cols[t]))
+        s = np.ascontiguousarray(_checked_cast(srcs, cols[1 - t]))
+        pr = np.ascontiguousarray(_checked_cast(pair_rows, cols[t]))
+        pt = np.ascontiguousarray(_checked_cast(pair_targets, cols[1 - t]))
+        return _lib.explain(self._h, t, r, s, np.ascontiguousarray(ratings, dtype=np.float32), pr, pt, num, reg, al, imp)
+
+    def _row_ratings(self, side, rid):
+        lib = load()
+        n = np.zeros(1, np.int64)
+        check(lib.als_get_row_ratings(self._h, side, int(rid), 0, None, None, ptr(n, C.c_int64)))
+        src, r = np.empty(max(int(n[0]), 1), np.int32), np.empty(max(int(n[0]), 1), np.float32)
+        check(lib.als_get_row_ratings(self._h, side, int(rid), int(n[0]), ptr(src, C.c_int32), ptr(r, C.c_float),
+                                      ptr(n, C.c_int64)))
+        return src[:int(n[0])], r[:int(n[0])]
+
+    def explain(self, pairs, dataset=None, num=10, side="user", regParam=None, alpha=None, implicitPrefs=None):
+        """One row per (userCol, itemCol) pair of `pairs`: the two ids, `score` (the fp64 total) and
+        `explanation`, the list of (src id, contribution) of the `num` ratings that contribute most: for
+        side="user" the user's items ("because you starred X"), for side="item" the item's users.  The
+        ratings come from `dataset` (userCol, itemCol, ratingCol); with dataset=None, on a model that still
+        holds the ratings it was fitted on (not a loaded one), each distinct row's own ratings are used."""
+        import pandas as pd
+        t = self._side(side)
+        cols = (self._p["userCol"], self._p["itemCol"])
+        self._fold_params(regParam, alpha, implicitPrefs)  # a missing parameter is named before a missing column
+        pr, pt = _column(pairs, cols[t]), _column(pairs, cols[1 - t])
+        if dataset is None:
+            if self._loaded:
+                raise ValueError("explain on a loaded ALSModel needs dataset: the saved model does not carry the ratings")
+            known = self._factors(t)[0]
+            rows, srcs, ratings = [], [], []
+            for rid in np.unique(_checked_cast(pr, cols[t])):
+                at = np.searchsorted(known, rid)
+                if at < known.size and known[at] == rid:  # a row the model does not know has no ratings here
+                    s, r = self._row_ratings(t, rid)
+                    rows.append(np.full(s.size, rid, np.int32))
+                    srcs.append(s)
+                    ratings.append(r)
+            rows, srcs, ratings = (np.concatenate(a) if a else np.zeros(0, d)
+                                   for a, d in ((rows, np.int32), (srcs, np.int32), (ratings, np.float32)))
+        else:
+            rows, srcs = _column(dataset, cols[t]), _column(dataset, cols[1 - t])
+            ratings = _column(dataset, self._p["ratingCol"])
+        total, ids, ev = self.explain_np(rows, srcs, ratings, pr, pt, num, t, regParam, alpha, implicitPrefs)
+        return pd.DataFrame({cols[t]: np.asarray(pr), cols[1 - t]: np.asarray(pt), "score": total,
+                             "explanation": [self._explanation(ids[p], ev[p]) for p in range(len(total))]})
+
+    def explain_timing(self):
+        """Device ms of the last explain: csr (map + sort + CSR of triples and pairs), gram (0 when cached),
+        solve (build, factor, solves, contributions, selection), total."""
+        return dict(zip(("csr", "gram", "solve", "total"), _lib.explain_timing(self._h).tolist()))
 
     def _recommend_transient(self, ids, f, numItems):
         """als_recommend of the given user rows on a model-only context of their own (numItems > 64)."""

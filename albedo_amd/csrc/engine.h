@@ -1,6 +1,6 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in; query_topk_host.cpp:
+// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation; query_topk_host.cpp:
 // top-k of caller-supplied vectors): error reporting, the device buffer, the row buckets, the per-side state, the
 // context and the few functions one file calls in another.  Not part of the public C ABI
 // (include/albedo_als.h).
@@ -225,6 +225,8 @@ struct als_ctx {
   double fold_ms[4] = {0, 0, 0, 0};
   // NNLS iterations of the last als_fold_in call: sum, maximum, rows solved, rows at the limit (0 after Cholesky)
   int64_t fold_stats[4] = {0, 0, 0, 0};
+  // device time of the last als_explain call (ms): map + sort + CSR of triples and pairs, src Gram, solve, total
+  double explain_ms[4] = {0, 0, 0, 0};
   // device time of the last als_recommend_vectors call (ms): exclusion map + sort, scan, merge, total
   double query_ms[4] = {0, 0, 0, 0};
   hipEvent_t evt[5] = {};

@@ -371,6 +371,50 @@ int fold_workgroups(int KP, int64_t n_rows, int n_cu);  // the persistent grid (
 size_t fold_scratch_doubles(int KP, int n_wg);
 hipError_t launch_fold_solve(int KP, const FoldArgs& a, int n_wg, hipStream_t s);
 
+// ---- explain (explain.hip): each rating's share of a fold-in row's score for a target (als_explain) ----
+constexpr int EXPLAIN_TB = 8;       // targets a workgroup solves and scores at a time
+constexpr int EXPLAIN_MAX_M = 64;   // entries of a list: one per lane of the wave that keeps it
+constexpr uint32_t EXPLAIN_NONE = 0xFFFFFFFFu;  // the row of a pair that cannot be explained
+// The pairs over the fold-in's CSR.  Sort key: the CSR row of the pair's row id (EXPLAIN_NONE when no triple has
+// that id or the model does not know the target) above the pair's input position, so the sorted order is
+// fixed, every row's pairs are a range and the pairs that cannot be explained end the list.
+struct ExplainPairs {
+  uint64_t *key, *key_sorted;  // [n_pairs]
+  uint32_t* target;            // [n_pairs] src row of the target, by input position
+  uint32_t *hi, *slot;         // [n_pairs] the two halves of the sorted keys: CSR row, input position
+  uint32_t* runs;              // [n_pairs] the distinct CSR rows ascending (the last may be EXPLAIN_NONE)
+  int32_t* counts;             // [n_pairs + 1]
+  int64_t* ptr;                // [n_pairs + 1] each listed row's range of the sorted pairs
+  int64_t* n_runs;             // device scalar
+  uint32_t *deg, *deg_sorted;  // [n_pairs] the listed rows' degrees (0 for EXPLAIN_NONE)
+  int32_t *iota, *order;       // [n_pairs] order: the listed rows by descending degree
+};
+size_t explain_sort_temp_bytes(int64_t n_pairs);
+// map + sort + run lengths + solve order of n_pairs > 0 pairs over the CSR rows row_ids [n_rows] (FoldCsr::ids,
+// ascending) with degrees row_deg; *n_runs_host is valid on return
+hipError_t explain_map_pairs(const int32_t* pair_row_id, const int32_t* pair_target_id, int64_t n_pairs,
+                             const int32_t* row_ids, const uint32_t* row_deg, int64_t n_rows, const int32_t* src_ids,
+                             int64_t n_src, void* temp, size_t temp_bytes, const ExplainPairs& e, int64_t* n_runs_host,
+                             hipStream_t s);
+struct ExplainArgs {
+  FoldArgs f;              // the fold-in's Y, G, CSR, k, parameters, scratch and bad (order, n_rows, X, stats unused)
+  const uint32_t* runs;    // ExplainPairs::runs, ptr, order, slot, target
+  const int64_t* pptr;
+  const int32_t* order;
+  int64_t n_runs;
+  const uint32_t* slot;
+  const uint32_t* target;
+  const int32_t* src_ids;  // raw ids of the src rows, ascending
+  int m;                   // 1 .. EXPLAIN_MAX_M
+  double* total;           // out [n_pairs], by input position
+  int32_t* ids;            // out [n_pairs][m]
+  double* contrib;         // out [n_pairs][m]
+};
+// total = NaN, ids = -1, contrib = NaN: what a pair that cannot be explained, and the padding, keep
+hipError_t launch_explain_fill(int64_t n_pairs, int m, double* total, int32_t* ids, double* contrib, hipStream_t s);
+// the persistent grid is the fold-in's (fold_workgroups, fold_scratch_doubles)
+hipError_t launch_explain(int KP, const ExplainArgs& a, int n_wg, hipStream_t s);
+
 // ---- query top-k (query_topk.hip): exact top-k of caller-supplied vectors (als_recommend_vectors) ------
 constexpr int QT_Q = 16;  // queries a workgroup scores at a time
 struct QueryPlan {

@@ -267,6 +267,58 @@ int als_fold_in_timing(const als_ctx* ctx, double* out4);
  * limit max(400, 20·rank).  All four are 0 after a Cholesky call. */
 int als_fold_in_stats(const als_ctx* ctx, int64_t* out4);
 
+/* Which ratings drive a recommendation: for a row of `side` given by its triples, as als_fold_in takes them,
+ * and a target of the other side, how much of the row's score for the target each rating contributes.  With
+ *   A_j = G + sum_i c_i y_i y_i^T + regParam·n_j·I
+ * the system als_fold_in builds for row j (c, w, n and G as als_audit_rows defines them), the score of target t
+ * is linear in the row's ratings,
+ *   s_jt = y_t^T x_j = y_t^T A_j^-1 sum_i w_i y_i = sum_i e_jti,   e_jti = w_i · y_t^T A_j^-1 y_i,
+ * and e_jti is rating i's share of it ("because you starred X").  Everything is fp64, in the original basis, at
+ * the model rank: A_j is built and factored exactly as the fold-in does, z = A_j^-1 y_t comes from two
+ * triangular solves, and e_i = w_i · sum_m y_i[m]·z[m], summed in ascending m.
+ *   Rows      (row_id, src_id, rating) [n], side and fp mean what they mean in als_fold_in: new or known ids, a
+ *             triple with an unknown src_id is dropped, a copy of a pair counts once per copy, the triples of a
+ *             row are summed in ascending src-row order.
+ *   Pairs     pair p asks about row pair_row_id[p] and the target pair_target_id[p], a raw id of the *src* side:
+ *             with side = ALS_USER an item ("why this item for this user").  A target among the row's own
+ *             sources is ordinary.  Only the rows that a valid pair names are built and factored.
+ *   Output    total_out[p] = sum_i e_i over the row's surviving triples in CSR order, one fixed order of
+ *             addition.  src_ids_out / contrib_out [n_pairs][m]: the m surviving triples with the largest e_i,
+ *             by (value desc, src id asc); -0.0 and +0.0 tie; a copy of a pair is an entry of its own; a shorter
+ *             list is padded with id -1 and value NaN (the NaN tells the padding: -1 is a valid raw id).
+ *             A pair whose row id occurs in no triple, or whose target the model does not know: total NaN, all
+ *             padding.  A row left with no surviving triple: total +0.0, all padding.
+ * Two calls give identical bits; no floating-point atomics are used.  A pair's output does not depend on the
+ * other pairs of the call, on their order, on ALBEDO_FOLD_WGS (which caps this grid as it caps the fold-in's),
+ * or on the order of the triples (except among copies of one pair with different ratings).  e_i depends only on
+ * rating i's own (w_i, y_i) and the pair's z: two ratings with equal factor rows and equal ratings give equal
+ * bits, and the id decides their order.
+ * The total is the fold-in's score before any rounding: als_fold_in rounds x_j to fp32 once, so
+ * |total - sum_m x_j[m]·y_t[m]| <= 2^-24 · sum_m |x_j[m]·y_t[m]| beyond the fp64 arithmetic.
+ * The model is read-only, as for als_fold_in: the call may form or use the side's fp64 src Gram cache (the
+ * fold-in's, with its validity rule); no factor, basis, sweep Gram, timing, path stat or top-k counter changes,
+ * als_fold_in_timing / als_fold_in_stats keep their values, and a call between two half-sweeps leaves the fit
+ * bit-identical.  Forks and contexts from als_model_create may call it; the latter need fp.
+ * Errors: ALS_E_INVALID_ARGUMENT for a bad side, a negative n or n_pairs, m < 1, null arrays with a positive
+ * count, null outputs with n_pairs > 0, a NaN or negative reg_param / alpha, fp == NULL on a model-only
+ * context.  ALS_E_UNSUPPORTED for m > 64, world > 1, n or n_pairs >= 2^31, and for fp->nonnegative != 0 or
+ * fp == NULL on a context with nonnegative = true: an NNLS row is not linear in its ratings, so this
+ * decomposition is not its score.  ALS_E_STATE when the src side has no factors.  ALS_E_NOT_POSITIVE_DEFINITE
+ * for a pivot <= 0 or NaN in a row that a valid pair names (a singular row that no pair names does not fail the
+ * call); the message names the lowest failing raw id, and the outputs are then unspecified.  n_pairs = 0 is
+ * ALS_OK. */
+int als_explain(als_ctx* ctx, int side, const als_fold_params* fp,
+                int64_t n, const int32_t* row_id, const int32_t* src_id, const float* rating,
+                int64_t n_pairs, const int32_t* pair_row_id, const int32_t* pair_target_id,
+                int32_t m,
+                double* total_out   /* [n_pairs] */,
+                int32_t* src_ids_out /* [n_pairs][m] */,
+                double* contrib_out  /* [n_pairs][m] */);
+/* Device time of the last als_explain call from HIP events on the context's stream (ms): out[0] = id mapping,
+ * sort and CSR of the triples and the pairs, out[1] = src Gram (0 when taken from the cache), out[2] = build,
+ * factor, solves, contributions and selection, out[3] = total. */
+int als_explain_timing(const als_ctx* ctx, double* out4);
+
 /* Exact top-k of caller-supplied query vectors against the factors of `dst_side` (ALS_ITEM: score against
  * the items, ALS_USER: against the users), with an optional exclusion list per query: recommendations for a
  * folded-in row without what it already has, for an average of rows, or for an item's own factor against
