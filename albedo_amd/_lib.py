@@ -26,6 +26,7 @@ ALS_E_NO_DEVICE = 7
 ALS_E_UNSUPPORTED = 8
 ALS_USER, ALS_ITEM = 0, 1
 ALS_METRIC_NDCG, ALS_METRIC_PRECISION, ALS_METRIC_MAP = 0, 1, 2
+ALS_EXCLUDE_RATINGS, ALS_EXCLUDE_PAIRS = 0, 1
 METRICS = {"NDCG@k": ALS_METRIC_NDCG, "Precision@k": ALS_METRIC_PRECISION, "MAP": ALS_METRIC_MAP}
 ALS_T_COUNT = 8
 # als_audit.worst_path: the solve path the row layout routes a row to (ALS_PATH_* in order)
@@ -139,6 +140,10 @@ SIGNATURES = [
     ("als_explain_timing", C.c_int, [P, F64P]),
     ("als_recommend_vectors", C.c_int, [P, C.c_int, C.c_int32, C.c_int64, F32P, I64P, I32P, I32P, F32P]),
     ("als_recommend_vectors_timing", C.c_int, [P, F64P]),
+    ("als_recommend_unseen", C.c_int, [P, C.c_int, C.c_int32, I32P, C.c_int64, C.c_int32, C.c_int64, I32P, I32P, I32P,
+                                       I32P, F32P]),
+    ("als_recommend_unseen_stats", C.c_int, [P, I64P]),
+    ("als_recommend_unseen_timing", C.c_int, [P, F64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
     ("als_evaluate_ranking", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P,
                                        C.c_int64]),

@@ -392,32 +392,89 @@ class ALSModel(_Params):
         keep = [i for i in range(len(src)) if recs[i]]
         return pd.DataFrame({src_col: src[keep], "recommendations": [recs[i] for i in keep]})
 
-    def recommendForAllUsers(self, numItems):
-        return self._rec_frame(*self._recommend(_lib.ALS_USER, numItems), self._p["userCol"], self._p["itemCol"])
-
-    def recommendForAllItems(self, numUsers):
-        return self._rec_frame(*self._recommend(_lib.ALS_ITEM, numUsers), self._p["itemCol"], self._p["userCol"])
-
-    def recommendForUserSubset(self, dataset, numItems, exclude=None):
-        """Spark's recommendForUserSubset.  exclude: a frame of (userCol, itemCol) rows; each user's lists then
-        leave out the items the frame gives them (their factors go through als_recommend_vectors as queries)."""
-        users = _column(dataset, self._p["userCol"])
+    def recommend_unseen_np(self, num, subset=None, side=_lib.ALS_USER, exclude=None):
+        """recommend_np without each src row's known pairs (als_recommend_unseen).  exclude=None leaves out the
+        dst rows of the row's ratings in the fitted context; exclude=(src ids, dst ids) leaves out those pairs
+        (any order, repeats and unknown ids allowed), which is what a loaded model needs."""
+        lib = load()
+        if subset is not None:
+            col = self._p["userCol"] if side == _lib.ALS_USER else self._p["itemCol"]
+            sub = np.ascontiguousarray(np.unique(_checked_cast(subset, col)))
+            nq = sub.size
+        else:
+            sub = None
+            nq = lib.als_num_rows(self._h, side)
+        mode, n_excl, es, ed = _lib.ALS_EXCLUDE_RATINGS, 0, None, None
         if exclude is not None:
-            uid, U = self.user_factors_np()
-            sub = np.unique(_checked_cast(users, self._p["userCol"]))
-            at = np.minimum(np.searchsorted(uid, sub), max(uid.size - 1, 0))
-            known = uid[at] == sub if uid.size else np.zeros(sub.size, bool)  # unknown users get no row
-            sub, at = sub[known], at[known]
-            excl = self._exclusions(sub, _column(exclude, self._p["userCol"]), _column(exclude, self._p["itemCol"]))
-            ids, sc = self.recommend_vectors_np(U[at], numItems, excl, "item")
-            return self._rec_frame(sub, ids, sc, self._p["userCol"], self._p["itemCol"])
-        return self._rec_frame(*self._recommend(_lib.ALS_USER, numItems, users), self._p["userCol"],
-                               self._p["itemCol"])
+            es = np.ascontiguousarray(exclude[0], dtype=np.int32).reshape(-1)
+            ed = np.ascontiguousarray(exclude[1], dtype=np.int32).reshape(-1)
+            if es.size != ed.size:
+                raise ValueError("exclude should be (src ids, dst ids) of one length")
+            mode, n_excl = _lib.ALS_EXCLUDE_PAIRS, int(es.size)
+        src = np.empty(nq, dtype=np.int32)
+        ids = np.empty((nq, max(int(num), 0)), dtype=np.int32)
+        sc = np.empty((nq, max(int(num), 0)), dtype=np.float32)
+        check(lib.als_recommend_unseen(self._h, side, int(num), ptr(sub, C.c_int32) if sub is not None else None, nq,
+                                       mode, n_excl, ptr(es, C.c_int32) if n_excl else None,
+                                       ptr(ed, C.c_int32) if n_excl else None, ptr(src, C.c_int32), ptr(ids, C.c_int32),
+                                       ptr(sc, C.c_float)))
+        return src, ids, sc
 
-    def recommendForItemSubset(self, dataset, numUsers):
-        items = _column(dataset, self._p["itemCol"])
-        return self._rec_frame(*self._recommend(_lib.ALS_ITEM, numUsers, items), self._p["itemCol"],
-                               self._p["userCol"])
+    def unseen_stats(self):
+        """als_recommend_unseen_stats of the last call: rows served, rows through the exact scan, list entries
+        the filter removed, dst rows the exact scan scored."""
+        out = np.zeros(4, dtype=np.int64)
+        check(load().als_recommend_unseen_stats(self._h, ptr(out, C.c_int64)))
+        return dict(zip(("rows", "rows_exact", "entries_removed", "dst_rows_scored"), out.tolist()))
+
+    def unseen_timing(self):
+        """als_recommend_unseen_timing of the last call, device ms per stage."""
+        out = np.zeros(5, dtype=np.float64)
+        check(load().als_recommend_unseen_timing(self._h, ptr(out, C.c_double)))
+        return dict(zip(("exclusions", "lists", "filter", "exact", "total"), out.tolist()))
+
+    def _cols(self, side):
+        u, i = self._p["userCol"], self._p["itemCol"]
+        return (u, i) if side == _lib.ALS_USER else (i, u)
+
+    def _recommend_all(self, side, num, excludeKnown):
+        rec = self.recommend_unseen_np(num, None, side) if excludeKnown else self._recommend(side, num)
+        return self._rec_frame(*rec, *self._cols(side))
+
+    def recommendForAllUsers(self, numItems, excludeKnown=False):
+        """Spark's recommendForAllUsers.  excludeKnown: each user's list leaves out the items of their ratings in
+        the fitted context (als_recommend_unseen); a loaded model holds none and raises."""
+        return self._recommend_all(_lib.ALS_USER, numItems, excludeKnown)
+
+    def recommendForAllItems(self, numUsers, excludeKnown=False):
+        return self._recommend_all(_lib.ALS_ITEM, numUsers, excludeKnown)
+
+    def _recommend_subset(self, side, dataset, num, exclude, excludeKnown):
+        src_col, dst_col = self._cols(side)
+        rows = _column(dataset, src_col)
+        if excludeKnown:
+            if exclude is not None:
+                raise ValueError("exclude and excludeKnown are alternatives: give one of them")
+            return self._rec_frame(*self.recommend_unseen_np(num, rows, side), src_col, dst_col)
+        if exclude is not None:  # the rows' factors go through als_recommend_vectors as queries
+            sid, F = self._factors(side)
+            sub = np.unique(_checked_cast(rows, src_col))
+            at = np.minimum(np.searchsorted(sid, sub), max(sid.size - 1, 0))
+            known = sid[at] == sub if sid.size else np.zeros(sub.size, bool)  # unknown ids get no row
+            sub, at = sub[known], at[known]
+            excl = self._exclusions(sub, _column(exclude, src_col), _column(exclude, dst_col))
+            ids, sc = self.recommend_vectors_np(F[at], num, excl, "item" if side == _lib.ALS_USER else "user")
+            return self._rec_frame(sub, ids, sc, src_col, dst_col)
+        return self._rec_frame(*self._recommend(side, num, rows), src_col, dst_col)
+
+    def recommendForUserSubset(self, dataset, numItems, exclude=None, excludeKnown=False):
+        """Spark's recommendForUserSubset.  exclude: a frame of (userCol, itemCol) rows; each user's lists then
+        leave out the items the frame gives them (their factors go through als_recommend_vectors as queries).
+        excludeKnown: leave out the items of each user's ratings in the fitted context (als_recommend_unseen)."""
+        return self._recommend_subset(_lib.ALS_USER, dataset, numItems, exclude, excludeKnown)
+
+    def recommendForItemSubset(self, dataset, numUsers, exclude=None, excludeKnown=False):
+        return self._recommend_subset(_lib.ALS_ITEM, dataset, numUsers, exclude, excludeKnown)
 
     # ---- RankingEvaluator on the device (RankingEvaluator.scala:83-139) ----------------------------
     def evaluate_ndcg(self, users, items, keys, k=30, per_user=False):

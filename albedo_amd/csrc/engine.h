@@ -229,6 +229,11 @@ struct als_ctx {
   double explain_ms[4] = {0, 0, 0, 0};
   // device time of the last als_recommend_vectors call (ms): exclusion map + sort, scan, merge, total
   double query_ms[4] = {0, 0, 0, 0};
+  // the last als_recommend_unseen call: known src rows served, rows sent to the exact scan, list entries the
+  // filter removed, dst rows the exact scan scored; device ms: exclusion map + sort, lists, filter, exact
+  // scan, total
+  int64_t unseen_stats[4] = {0, 0, 0, 0};
+  double unseen_ms[5] = {0, 0, 0, 0, 0};
   hipEvent_t evt[5] = {};
   // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
   // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was

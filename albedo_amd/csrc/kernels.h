@@ -236,6 +236,32 @@ hipError_t launch_iota_i32(int32_t* out, int64_t n, int64_t start, hipStream_t s
 // persistent exact scan over them
 hipError_t launch_topk_exact_flagged(int KP, const TopkArgs& a, const int32_t* need, int64_t n, int32_t* flags, int* cnt,
                                      int n_cu, hipStream_t s);
+// ---- top-k without known pairs (topk.hip, als_recommend_unseen) -------------------------------------
+// The dst rows src row u excludes: entries [ptr[u], ptr[u + 1]) of `col` (ratings mode: the side's CSR,
+// ascending within a row, copies allowed) or of the low halves of `key` (pairs mode: sorted keys
+// src row << 32 | dst row); exactly one of col / key is set
+struct UnseenExcl {
+  const int64_t* ptr;
+  const int32_t* col;
+  const uint64_t* key;
+};
+size_t unseen_sort_temp_bytes(int64_t n_e);
+// n_e > 0 raw (src id, dst id) pairs -> key_sorted [n_e] and ptr [n_src + 1]; a pair with an unknown id
+// sorts past ptr[n_src]
+hipError_t unseen_pair_ranges(const int32_t* esrc, const int32_t* edst, int64_t n_e, const int32_t* src_ids, int64_t n_src,
+                              const int32_t* dst_ids, int64_t n_dst, uint64_t* key, uint64_t* key_sorted, void* temp,
+                              size_t temp_bytes, int64_t* ptr, hipStream_t s);
+// lists [n][depth] (raw ids, NaN-score padded) of the src rows src_rows[0 .. n) -> the first k entries not
+// excluded into out [n][k] (-1 / NaN padded); a row it cannot certify: flags[atomicAdd(cnt, 1)] = its
+// position.  stat[0] += entries removed, stat[2] += rows flagged
+hipError_t launch_unseen_filter(const int32_t* list_ids, const float* list_scores, int depth, int k, int64_t n, int64_t n_dst,
+                                const int32_t* src_rows, const int32_t* dst_ids, const UnseenExcl& x, int32_t* out_ids,
+                                float* out_scores, int32_t* flags, int* cnt, unsigned long long* stat, hipStream_t s);
+// exact scan of the flagged positions flags[0 .. cnt[0]) (cnt[1]: the persistent grid's work counter, zero on
+// entry; n: an upper bound of the count) over the dst rows each row does not exclude, into a.out_ids /
+// a.out_scores [*][a.k]; *scored += dst rows scored
+hipError_t launch_unseen_exact(int KP, const TopkArgs& a, const UnseenExcl& x, const int32_t* flags, int* cnt,
+                               unsigned long long* scored, int64_t n, int n_cu, hipStream_t s);
 // ---- evaluation (eval.hip): RankingEvaluator.scala:83-139 on the device ----------------------------
 size_t eval_sort_temp_bytes(int64_t n);
 // user ids -> rows of the ascending `ids`, grouped: runs[r] (row) with counts[r] entries at

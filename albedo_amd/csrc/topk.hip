@@ -1478,4 +1478,275 @@ hipError_t launch_topk_exact(int KP, const TopkArgs& a, const int32_t* rows, int
   return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------------------------
+// als_recommend_unseen: top-k without each src row's known dst rows (include/albedo_als.h).
+//   pair keys  raw (src id, dst id) pairs -> key (src row << 32 | dst row), all ones when either id is
+//              unknown; one radix sort; ptr[u] = the first key of src row u (the unknown keys sort last,
+//              past ptr[n_src])
+//   filter     one wave per src row, one lane per entry of its certified top-`depth` list: the entry's id
+//              is searched in the row's exclusion range (both ascend), the survivors are compacted by
+//              ballot + prefix popcount and the first k written out.  A row whose list was full and
+//              keeps fewer than k cannot be certified: its position goes onto the flag list
+//   exact      topk_exact_kernel<KP, 1> on the flagged rows, with one difference: a dst row whose score
+//              reaches the wave's threshold is looked up in the exclusion range before it is buffered,
+//              and dropped when found.  The threshold therefore only rises on rows that may be listed.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t unseen_row_at(const UnseenExcl& x, int64_t i) {
+  return x.col ? (uint32_t)x.col[i] : (uint32_t)x.key[i];
+}
+// dst row r is in the ascending range [e0, e1)
+__device__ __forceinline__ bool unseen_has_row(const UnseenExcl& x, int64_t e0, int64_t e1, uint32_t r) {
+  int64_t lo = e0, hi = e1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (unseen_row_at(x, mid) < r) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < e1 && unseen_row_at(x, lo) == r;
+}
+// the dst row of raw id `id` is in the range (dst ids ascend with the row)
+__device__ __forceinline__ bool unseen_has_id(const UnseenExcl& x, int64_t e0, int64_t e1, const int32_t* __restrict__ dst_ids,
+                                              int32_t id) {
+  int64_t lo = e0, hi = e1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (dst_ids[unseen_row_at(x, mid)] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < e1 && dst_ids[unseen_row_at(x, lo)] == id;
+}
+
+__device__ __forceinline__ int64_t unseen_find_id(const int32_t* __restrict__ ids, int64_t n, int32_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ids[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && ids[lo] == v ? lo : -1;
+}
+__global__ void unseen_pair_key_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ edst, int64_t n_e,
+                                       const int32_t* __restrict__ src_ids, int64_t n_src,
+                                       const int32_t* __restrict__ dst_ids, int64_t n_dst, uint64_t* __restrict__ key) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u = unseen_find_id(src_ids, n_src, esrc[i]), d = unseen_find_id(dst_ids, n_dst, edst[i]);
+    key[i] = (u < 0 || d < 0) ? ~(uint64_t)0 : ((uint64_t)u << 32) | (uint64_t)d;
+  }
+}
+__global__ void unseen_pair_ptr_kernel(const uint64_t* __restrict__ key, int64_t n_e, int64_t n_src, int64_t* __restrict__ ptr) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u <= n_src; u += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t first = (uint64_t)u << 32;
+    int64_t lo = 0, hi = n_e;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (key[mid] < first) lo = mid + 1;
+      else hi = mid;
+    }
+    ptr[u] = lo;
+  }
+}
+
+// stat[0] += list entries removed, stat[2] += rows flagged; cnt[0] += rows flagged (this pass)
+__global__ __launch_bounds__(256) void unseen_filter_kernel(const int32_t* __restrict__ lid, const float* __restrict__ lsc,
+                                                            int depth, int k, int64_t n, int64_t n_dst,
+                                                            const int32_t* __restrict__ src_rows,
+                                                            const int32_t* __restrict__ dst_ids, UnseenExcl x,
+                                                            int32_t* __restrict__ out_ids, float* __restrict__ out_scores,
+                                                            int32_t* __restrict__ flags, int* __restrict__ cnt,
+                                                            unsigned long long* __restrict__ stat) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  unsigned long long removed = 0, flagged = 0;
+  for (int64_t i = wave0; i < n; i += n_waves) {
+    const int64_t u = src_rows[i];
+    const int64_t e0 = x.ptr[u], e1 = x.ptr[u + 1];
+    int32_t id = -1;
+    float sc = __int_as_float(0x7fc00000);
+    if (lane < depth) {
+      id = lid[i * depth + lane];
+      sc = lsc[i * depth + lane];
+    }
+    const bool valid = lane < depth && !(sc != sc);  // a NaN score is the list's padding
+    const bool excl = valid && e1 > e0 && unseen_has_id(x, e0, e1, dst_ids, id);
+    const uint64_t keep = __ballot(valid && !excl);
+    const int n_keep = __popcll(keep), pos = __popcll(keep & ((1ull << lane) - 1ull));
+    removed += (unsigned long long)__popcll(__ballot(excl));
+    if (valid && !excl && pos < k) {
+      out_ids[i * k + pos] = id;
+      out_scores[i * k + pos] = sc;
+    }
+    if (lane >= n_keep && lane < k) {
+      out_ids[i * k + lane] = -1;
+      out_scores[i * k + lane] = __int_as_float(0x7fc00000);
+    }
+    // a list shorter than depth holds every dst row (n_dst <= depth): its survivors are the answer
+    if (n_keep < k && n_dst > depth) {
+      if (lane == 0) flags[atomicAdd(cnt, 1)] = (int32_t)i;
+      ++flagged;
+    }
+  }
+  if (lane == 0) {
+    if (removed) atomicAdd(stat, removed);
+    if (flagged) atomicAdd(stat + 2, flagged);
+  }
+}
+
+// topk_exact_kernel<KP, 1> over the flagged positions rows[0 .. *dcount) (persistent grid, work counter
+// *dnext), each src row with its exclusion range; *scored += dst rows scored
+template <int KP>
+__global__ __launch_bounds__(256) void unseen_exact_kernel(TopkArgs a, UnseenExcl x, const int32_t* rows, const int* dcount,
+                                                           int* dnext, unsigned long long* scored) {
+  constexpr int P = 1;
+  __shared__ float msc[4][64 * P];
+  __shared__ int mix[4][64 * P];
+  __shared__ __attribute__((aligned(16))) float s_stage[4][64 * TK_SEL_LD + KP];  // f2j_dot_rows
+  __shared__ int s_idx;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long n_scored = 0;
+  for (;;) {
+    if (threadIdx.x == 0) s_idx = atomicAdd(dnext, 1);
+    __syncthreads();
+    const int idx = s_idx;
+    __syncthreads();  // s_idx read by every thread before the next claim rewrites it
+    if (idx >= *dcount) break;  // workgroup-uniform
+    const int64_t si = rows[idx];
+    const int srow = a.src_rows[si];
+    const float* s = a.S + (int64_t)srow * KP;
+    const int64_t e0 = x.ptr[srow], e1 = x.ptr[srow + 1];
+    float bs[2 * P];
+    int bi[2 * P];
+#pragma unroll
+    for (int h = 0; h < 2 * P; ++h) { bs[h] = -INFINITY; bi[h] = -1; }
+    // the kept list's last score once full.  No starting threshold: the filtered list gives no lower
+    // bound of the k-th score over the rows left
+    float thr = -INFINITY;
+    float sfe[TOPK_M + 1];
+    float marg = 0.f;
+    if (a.cfeat) {  // this row's bound features (fp64, like the order kernel's)
+      double nn = 0.0, sp[TOPK_M] = {};
+      for (int c = lane; c < a.kreal; c += 64) {
+        const double v = (double)s[c];
+        nn += v * v;
+#pragma unroll
+        for (int d = 0; d < TOPK_M; ++d) sp[d] += v * a.VP[d * KP + c];
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        nn += __shfl_xor(nn, o);
+#pragma unroll
+        for (int d = 0; d < TOPK_M; ++d) sp[d] += __shfl_xor(sp[d], o);
+      }
+      double pp = 0.0;
+#pragma unroll
+      for (int d = 0; d < TOPK_M; ++d) {
+        sfe[d] = (float)sp[d];
+        pp += sp[d] * sp[d];
+      }
+      sfe[TOPK_M] = __double2float_ru(sqrt(fmax(nn - pp, 0.0) + 1e-13 * nn));
+      marg = (float)(1.2e-5 * sqrt(nn) * (double)a.tmax_norm) * 1.0001f + 1e-30f;
+    }
+    // 64 dst rows (one per lane) -> F2J scores; a batch with a score at the threshold is buffered, its
+    // qualifying rows looked up in the exclusion range first (excluded: score -inf, index -1)
+    auto score64 = [&](int64_t pj, bool in) {
+      const int64_t dj = (a.perm && in) ? (int64_t)a.perm[pj] : pj;
+      float sc = f2j_dot_rows<KP>(s, a.T, in ? (int)dj : -1, a.kreal, s_stage[wave]);
+      n_scored += (unsigned long long)__popcll(__ballot(in));
+      if (!__any(sc >= thr)) return;
+      int di = in ? (int)dj : -1;
+      if (in && sc >= thr && e1 > e0 && unseen_has_row(x, e0, e1, (uint32_t)dj)) {
+        sc = -INFINITY;
+        di = -1;
+      }
+      bs[P] = sc;
+      bi[P] = di;
+      wave_bitonic<2 * P>(bs, bi);
+      bs[P] = -INFINITY;
+      bi[P] = -1;
+      thr = rdlane(bs[P - 1], 63);
+    };
+    if (a.cfeat) {
+      // chunk-major, as topk_exact_kernel: a lane per chunk bound, 64 chunks at a time
+      const int ch = topk_chunk_rows_dev<KP>();
+      for (int64_t c0 = (int64_t)wave * 64; c0 < a.n_chunks; c0 += 256) {
+        const int64_t c = c0 + lane;
+        float b = INFINITY;
+        if (c < a.n_chunks) b = tk_bound(sfe, a.cfeat + c * TOPK_CF) + marg;
+        uint64_t m = __ballot(c < a.n_chunks && !(b < thr));
+        while (m) {
+          const int l = __builtin_ctzll(m);
+          m &= m - 1;
+          if (rdlane(b, l) < thr) continue;  // the threshold rose past this chunk's bound
+          const int64_t cc = c0 + l;
+          for (int r0 = 0; r0 < ch; r0 += 64) {
+            const int64_t pj = cc * ch + r0 + lane;
+            score64(pj, r0 + lane < ch && pj < a.n_dst);
+          }
+        }
+      }
+    } else {
+      for (int64_t j0 = (int64_t)wave * 64; j0 < a.n_dst; j0 += 256) score64(j0 + lane, j0 + lane < a.n_dst);
+    }
+    msc[wave][lane] = bs[0];
+    mix[wave][lane] = bi[0];
+    __syncthreads();
+    if (wave == 0) {  // fold the other waves' lists in, one bitonic sort of 128 slots each
+      for (int w = 1; w < 4; ++w) {
+        bs[P] = msc[w][lane];
+        bi[P] = mix[w][lane];
+        wave_bitonic<2 * P>(bs, bi);
+      }
+      if (lane < a.k) {
+        const int ix = bi[0];
+        a.out_ids[si * a.k + lane] = ix >= 0 ? a.dst_ids[ix] : -1;
+        a.out_scores[si * a.k + lane] = ix >= 0 ? bs[0] : __int_as_float(0x7fc00000);
+      }
+    }
+    __syncthreads();  // msc / mix read by wave 0 before the next row's waves rewrite them
+  }
+  if (scored && lane == 0 && n_scored) atomicAdd(scored, n_scored);
+}
+
+size_t unseen_sort_temp_bytes(int64_t n_e) {
+  size_t a = 0;
+  (void)rocprim::radix_sort_keys(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max<int64_t>(n_e, 1), 0, 64,
+                                 (hipStream_t)0);
+  return a;
+}
+
+hipError_t unseen_pair_ranges(const int32_t* esrc, const int32_t* edst, int64_t n_e, const int32_t* src_ids, int64_t n_src,
+                              const int32_t* dst_ids, int64_t n_dst, uint64_t* key, uint64_t* key_sorted, void* temp,
+                              size_t temp_bytes, int64_t* ptr, hipStream_t s) {
+  if (n_e <= 0 || n_e > (int64_t)0x7FFFFFFF || n_src < 0 || n_src >= (int64_t)0x7FFFFFFF || n_dst >= (int64_t)0x7FFFFFFF)
+    return hipErrorInvalidValue;
+  unseen_pair_key_kernel<<<tk_grid(n_e, 256), 256, 0, s>>>(esrc, edst, n_e, src_ids, n_src, dst_ids, n_dst, key);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  size_t tb = temp_bytes;
+  e = rocprim::radix_sort_keys(temp, tb, key, key_sorted, (size_t)n_e, 0, 64, s);
+  if (e != hipSuccess) return e;
+  unseen_pair_ptr_kernel<<<tk_grid(n_src + 1, 256), 256, 0, s>>>(key_sorted, n_e, n_src, ptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_unseen_filter(const int32_t* list_ids, const float* list_scores, int depth, int k, int64_t n, int64_t n_dst,
+                                const int32_t* src_rows, const int32_t* dst_ids, const UnseenExcl& x, int32_t* out_ids,
+                                float* out_scores, int32_t* flags, int* cnt, unsigned long long* stat, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (k < 1 || depth < k || depth > TOPK_KC) return hipErrorInvalidValue;
+  unseen_filter_kernel<<<tk_grid(n * 64, 256), 256, 0, s>>>(list_ids, list_scores, depth, k, n, n_dst, src_rows, dst_ids, x,
+                                                            out_ids, out_scores, flags, cnt, stat);
+  return hipGetLastError();
+}
+
+hipError_t launch_unseen_exact(int KP, const TopkArgs& a, const UnseenExcl& x, const int32_t* flags, int* cnt,
+                               unsigned long long* scored, int64_t n, int n_cu, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (a.k < 1 || a.k > TOPK_KC) return hipErrorInvalidValue;
+  const int grid = (int)std::min<int64_t>(n, (int64_t)4 * std::max(n_cu, 1));
+  if (KP == 64) unseen_exact_kernel<64><<<grid, 256, 0, s>>>(a, x, flags, cnt, cnt + 1, scored);
+  else if (KP == 128) unseen_exact_kernel<128><<<grid, 256, 0, s>>>(a, x, flags, cnt, cnt + 1, scored);
+  else if (KP == 256) unseen_exact_kernel<256><<<grid, 256, 0, s>>>(a, x, flags, cnt, cnt + 1, scored);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 }  // namespace albedo

@@ -1,6 +1,7 @@
 // Host side of top-k (topk.hip) and NDCG (eval.hip): the per-call plan of the dst side, the passes over
 // the src rows, the three ways a call's lists reach the caller's arrays, and the C ABI entry points
-// als_recommend, als_evaluate_ndcg, als_evaluate_ranking and the top-k counters.
+// als_recommend, als_recommend_unseen (the same passes at the filter's depth, their lists filtered on the
+// device), als_evaluate_ndcg, als_evaluate_ranking and the top-k counters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -716,11 +717,227 @@ int allgather_lists(als_ctx* c, int64_t n, int k, const int64_t* pos, int32_t* i
   return ALS_OK;
 }
 
+// ---- als_recommend_unseen -------------------------------------------------------------------------
+
+namespace {
+
+// Stage marks on a stream, as many as the passes need
+struct MarkList {
+  std::vector<hipEvent_t> e;
+  MarkList() = default;
+  MarkList(const MarkList&) = delete;
+  MarkList& operator=(const MarkList&) = delete;
+  ~MarkList() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t mark(hipStream_t s) {
+    hipEvent_t x;
+    const hipError_t r = hipEventCreate(&x);
+    if (r != hipSuccess) return r;
+    e.push_back(x);
+    return hipEventRecord(x, s);
+  }
+};
+
+// Declared after the buffers a call queues work on, so that it goes first
+struct DrainStream {
+  hipStream_t s;
+  ~DrainStream() {
+    if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+// The depth of the filter's lists: ALBEDO_UNSEEN_DEPTH, else 48, clamped to [k, TOPK_KC].  A tuning choice:
+// no result depends on it.  c2, all users, k = 30: the lists cost 9.7 ms of device time at 48 and 294 ms at
+// 64, where the running threshold sits at the last place of the 64-entry candidate lists (topk_threshold_rank)
+// and certification has no gap left; the 0.9 % of the rows that 48 sends to the exact scan cost 8.7 ms
+// ("Recommendations without the known pairs", profiles/unseen_c2.json).
+int unseen_depth(int k) {
+  int d = 48;
+  const char* e = std::getenv("ALBEDO_UNSEEN_DEPTH");
+  if (e && *e) d = std::atoi(e);
+  return std::max(k, std::min(TOPK_KC, d));
+}
+
+}  // namespace
+
+// Tier 1: the certified top-`depth` lists of the existing passes, kept on the device and filtered there.
+// Tier 2: the rows the filter cannot certify, through an exact scan that knows each row's exclusion range.
+int recommend_unseen(als_ctx* c, int src, int k, const int32_t* subset, int64_t n_subset, int mode, int64_t n_excl,
+                     const int32_t* excl_src, const int32_t* excl_dst, int32_t* src_ids_out, int32_t* ids_out,
+                     float* scores_out) {
+  TRYC(materialize(c, src));
+  Side& S = c->s[src];
+  Side& T = c->s[1 - src];
+  hipStream_t st = c->st;
+  const int KP = c->KP, depth = unseen_depth(k);
+  const bool all_rows = subset == nullptr;
+  const int64_t nq = all_rows ? S.n : n_subset;
+  std::vector<int32_t> known;
+  std::vector<int64_t> pos;
+  if (!all_rows) map_subset(S, subset, nq, k, ids_out, scores_out, known, pos);
+  if (src_ids_out && nq > 0) std::memcpy(src_ids_out, all_rows ? S.ids.data() : subset, (size_t)nq * 4);
+  const int64_t n_known = all_rows ? nq : (int64_t)known.size();
+  const int32_t* rows = all_rows ? nullptr : known.data();
+  const int64_t* out_pos = n_known == nq ? nullptr : pos.data();
+  c->last_rescan.clear();
+  c->last_rescan_ready = true;
+  c->unseen_stats[0] = n_known;
+  if (n_known == 0) return ALS_OK;
+  if (T.n == 0) {
+    std::fill(ids_out, ids_out + nq * k, -1);
+    std::fill(scores_out, scores_out + nq * k, NAN);
+    return ALS_OK;
+  }
+  TopkPlan P;
+  DevBuf d_es, d_ed, d_sids, d_key, d_keys, d_tmp, d_ptr, d_lid, d_lsc, d_flag, d_cnt, d_stat;
+  MarkList clk;
+  TopkOutput out(c, ids_out, scores_out, k, 0, out_pos, INT64_MAX);  // never pinned: the synchronous sink
+  DrainStream queued{st};
+  HIPCHK(clk.mark(st));  // 0
+  TRYC(topk_plan(c, src, depth, P));
+  HIPCHK(clk.mark(st));  // 1
+  UnseenExcl x{};
+  if (mode == ALS_EXCLUDE_RATINGS) {
+    x.ptr = S.d_ptr.as<int64_t>();
+    x.col = S.d_col.as<int32_t>();
+  } else {
+    HIPCHK(d_ptr.ensure((size_t)(S.n + 1) * 8));
+    x.ptr = d_ptr.as<int64_t>();
+    if (n_excl == 0) {
+      HIPCHK(hipMemsetAsync(d_ptr.p, 0, (size_t)(S.n + 1) * 8, st));  // every range empty: nothing is looked up
+    } else {
+      const size_t tb = unseen_sort_temp_bytes(n_excl);
+      HIPCHK(d_es.ensure((size_t)n_excl * 4));
+      HIPCHK(d_ed.ensure((size_t)n_excl * 4));
+      HIPCHK(d_sids.ensure((size_t)S.n * 4));
+      HIPCHK(d_key.ensure((size_t)n_excl * 8));
+      HIPCHK(d_keys.ensure((size_t)n_excl * 8));
+      HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
+      HIPCHK(hipMemcpyAsync(d_es.p, excl_src, (size_t)n_excl * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_ed.p, excl_dst, (size_t)n_excl * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_sids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(unseen_pair_ranges(d_es.as<int32_t>(), d_ed.as<int32_t>(), n_excl, d_sids.as<int32_t>(), S.n,
+                                P.d_dstids.as<int32_t>(), T.n, d_key.as<uint64_t>(), d_keys.as<uint64_t>(), d_tmp.p, tb,
+                                d_ptr.as<int64_t>(), st));
+      x.key = d_keys.as<uint64_t>();
+    }
+  }
+  HIPCHK(clk.mark(st));  // 2
+  HIPCHK(d_cnt.ensure(8));
+  HIPCHK(d_stat.ensure(24));
+  HIPCHK(hipMemsetAsync(d_stat.p, 0, 24, st));
+  const int64_t chunk = topk_rows_per_pass(c);
+  const int64_t n_pass = (n_known + chunk - 1) / chunk;
+  TRYC(topk_begin(c, P, n_known, n_pass, rows));
+  for (int64_t it = 0; it < n_pass; ++it) {  // marks 3 + 4·it ..: lists, filter, exact scan, copies
+    const int64_t q0 = it * chunk, nc = std::min<int64_t>(chunk, n_known - q0);
+    HIPCHK(d_lid.ensure((size_t)nc * depth * 4));
+    HIPCHK(d_lsc.ensure((size_t)nc * depth * 4));
+    HIPCHK(d_flag.ensure((size_t)nc * 4));
+    TopkPassOut lists;
+    lists.ids = d_lid.as<int32_t>();
+    lists.scores = d_lsc.as<float>();
+    TRYC(topk_run_rows(c, P, rows ? rows + q0 : nullptr, q0, q0, nc, lists));
+    HIPCHK(clk.mark(st));
+    TopkPassOut o;
+    TRYC(out.begin_pass(0, q0, nc, o));
+    const int32_t* src_rows = P.pb[0].d_src.as<int32_t>();
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8, st));
+    HIPCHK(launch_unseen_filter(d_lid.as<int32_t>(), d_lsc.as<float>(), depth, k, nc, T.n, src_rows,
+                                P.d_dstids.as<int32_t>(), x, o.ids, o.scores, d_flag.as<int32_t>(), d_cnt.as<int>(),
+                                d_stat.as<unsigned long long>(), st));
+    HIPCHK(clk.mark(st));
+    TopkArgs a{};
+    a.S = S.d_orig.as<float>();
+    a.T = T.d_orig.as<float>();
+    a.src_rows = src_rows;
+    a.n_src = nc;
+    a.n_dst = T.n;
+    a.dst_ids = P.d_dstids.as<int32_t>();
+    a.kreal = c->p.rank;
+    a.k = k;
+    a.tmax_norm = (float)(P.tmax * (1.0 + 1e-6));
+    a.perm = P.d_perm.as<uint32_t>();
+    a.n_chunks = P.n_chunks;
+    a.VP = P.d_VP.as<double>();
+    a.cfeat = P.prune ? P.d_cfeat.as<float>() : nullptr;
+    a.out_ids = o.ids;
+    a.out_scores = o.scores;
+    HIPCHK(launch_unseen_exact(KP, a, x, d_flag.as<int32_t>(), d_cnt.as<int>(), d_stat.as<unsigned long long>() + 1, nc,
+                               c->n_cu, st));
+    HIPCHK(clk.mark(st));
+    TRYC(out.end_pass(0, q0, nc));
+    HIPCHK(clk.mark(st));
+  }
+  TRYC(topk_finish(c, P));
+  unsigned long long stat[3] = {0, 0, 0};
+  HIPCHK(copy_st(c, stat, d_stat.p, 24, hipMemcpyDeviceToHost));
+  c->unseen_stats[1] = (int64_t)stat[2];
+  c->unseen_stats[2] = (int64_t)stat[0];
+  c->unseen_stats[3] = (int64_t)stat[1];
+  const std::vector<hipEvent_t>& e = clk.e;
+  c->unseen_ms[0] = mode == ALS_EXCLUDE_PAIRS && n_excl > 0 ? event_ms(e[1], e[2]) : 0.0;
+  c->unseen_ms[1] = event_ms(e[0], e[1]);
+  for (int64_t it = 0; it < n_pass; ++it) {
+    const hipEvent_t* m = e.data() + 3 + 4 * it;
+    c->unseen_ms[1] += event_ms(m[-1], m[0]);
+    c->unseen_ms[2] += event_ms(m[0], m[1]);
+    c->unseen_ms[3] += event_ms(m[1], m[2]);
+  }
+  c->unseen_ms[4] = event_ms(e.front(), e.back());
+  return ALS_OK;
+}
+
 }  // namespace albedo
 
 using namespace albedo;
 
 extern "C" {
+
+int als_recommend_unseen(als_ctx* c, int side, int32_t k, const int32_t* subset, int64_t n_subset, int32_t mode,
+                         int64_t n_excl, const int32_t* excl_src, const int32_t* excl_dst, int32_t* src_ids_out,
+                         int32_t* dst_ids_out, float* scores_out) {
+  if (!c || (side != 0 && side != 1) || !dst_ids_out || !scores_out) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  if (mode != ALS_EXCLUDE_RATINGS && mode != ALS_EXCLUDE_PAIRS)
+    return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_unseen: unknown exclusion mode " + std::to_string(mode));
+  if (k < 1) return fail(ALS_E_INVALID_ARGUMENT, "num must be positive");
+  if ((subset && n_subset < 0) || n_excl < 0)
+    return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_unseen: a count is negative");
+  if (mode == ALS_EXCLUDE_PAIRS && n_excl > 0 && (!excl_src || !excl_dst))
+    return fail(ALS_E_INVALID_ARGUMENT, "als_recommend_unseen: null exclusion pairs with n_excl > 0");
+  if (k > TOPK_KC)
+    return fail(ALS_E_UNSUPPORTED, "als_recommend_unseen keeps at most " + std::to_string(TOPK_KC) + " rows per list (k <= 64)");
+  if (c->world > 1) return fail(ALS_E_UNSUPPORTED, "als_recommend_unseen is single-process (world = 1)");
+  if (mode == ALS_EXCLUDE_PAIRS && n_excl > (int64_t)0x7FFFFFFF)
+    return fail(ALS_E_UNSUPPORTED, "als_recommend_unseen takes at most 2^31 - 1 exclusion pairs a call");
+  for (int s = 0; s < 2; ++s)
+    if (!c->s[s].has_factors)
+      return fail(ALS_E_STATE, std::string("als_recommend_unseen needs the ") + (s == ALS_USER ? "user" : "item") +
+                                   " factors (fit, inject or load them first)");
+  if (mode == ALS_EXCLUDE_RATINGS && (!c->has_ratings || c->model_only))
+    return fail(ALS_E_STATE,
+                "als_recommend_unseen: this context holds no ratings to exclude (a loaded model); pass the known pairs "
+                "(ALS_EXCLUDE_PAIRS)");
+  TRYC(set_device(c));
+  for (int64_t& v : c->unseen_stats) v = 0;
+  for (double& v : c->unseen_ms) v = 0.0;
+  return recommend_unseen(c, side, k, subset, n_subset, mode, mode == ALS_EXCLUDE_PAIRS ? n_excl : 0, excl_src, excl_dst,
+                          src_ids_out, dst_ids_out, scores_out);
+}
+
+int als_recommend_unseen_stats(const als_ctx* c, int64_t* out4) {
+  if (!c || !out4) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  for (int i = 0; i < 4; ++i) out4[i] = c->unseen_stats[i];
+  return ALS_OK;
+}
+
+int als_recommend_unseen_timing(const als_ctx* c, double* out5) {
+  if (!c || !out5) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  for (int i = 0; i < 5; ++i) out5[i] = c->unseen_ms[i];
+  return ALS_OK;
+}
 
 int als_recommend(als_ctx* c, int side, int32_t k, const int32_t* subset, int64_t n_subset, int32_t* src_ids_out,
                   int32_t* dst_ids_out, float* scores_out) {

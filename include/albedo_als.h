@@ -160,6 +160,51 @@ int als_model_create(int32_t rank, int64_t n_users, const int32_t* user_ids, con
  * k > 512: ALS_E_UNSUPPORTED. */
 int als_recommend(als_ctx* ctx, int side, int32_t k, const int32_t* subset, int64_t n_subset,
                   int32_t* src_ids_out, int32_t* dst_ids_out, float* scores_out);
+/* als_recommend without each src row's known pairs: for src row u the first k dst rows not in its excluded
+ * set E_u, in the total order of als_recommend (F2J score desc, raw id asc).  side, subset, n_subset,
+ * src_ids_out and the [n][k] outputs mean what they mean in als_recommend: subset == NULL is every src row in
+ * ascending id order, an unknown subset id gives an all-padding row, a repeated id one row each, padding is
+ * id -1 / score NaN and a list is dense.
+ *   E_u, mode ALS_EXCLUDE_RATINGS  every dst row that occurs in a rating of u in the context's ingest, whatever
+ *                 the rating's value (zero and negative ratings are known pairs too); a repeated pair counts
+ *                 once.  n_excl, excl_src and excl_dst are ignored.
+ *   E_u, mode ALS_EXCLUDE_PAIRS    the dst ids paired with u's raw id in (excl_src, excl_dst) [n_excl], raw ids of
+ *                 the src and the dst side.  Any order, repeats allowed, a pair with an id unknown on either side
+ *                 is ignored; the result does not depend on the order of the pairs.  n_excl = 0: E is empty
+ *                 everywhere.
+ *   Result        the score is the F2J sdot of als_recommend / als_recommend_vectors (fp32, left to right, no
+ *                 FMA), so a row's list equals, ids and score bits, als_recommend_vectors with u's factor as
+ *                 als_get_factors returns it and E_u as the exclusion list, and als_recommend when E_u is empty.
+ *                 Fewer than k dst rows left: a shorter, padded list; all excluded: all padding.
+ * The contract covers finite factors; non-finite factors are outside it (als_recommend_vectors never lists a
+ * NaN score, als_recommend's order kernel has its own rules).
+ * Limits: 1 <= k <= 64 and world = 1, ALS_E_UNSUPPORTED beyond either; n_excl >= 2^31 is ALS_E_UNSUPPORTED.
+ * ALS_E_STATE when either side has no factors, and for ALS_EXCLUDE_RATINGS on a context without ratings (from
+ * als_model_create).  ALS_E_INVALID_ARGUMENT for a bad side or mode, k < 1, a negative count, null pair arrays
+ * with n_excl > 0, null outputs.  Forks may call it; they view the parent's ratings.
+ * Two calls give identical bits; no floating-point atomics are used.  The model is read-only: factors, bases,
+ * Gram caches, sweep timings, path stats and the fold-in / explain / query timings are unchanged, and a call
+ * between two half-sweeps leaves the fit bit-identical.  The call runs the top-k passes of als_recommend (as
+ * als_evaluate_ndcg does), so als_topk_stats, als_topk_timing and als_topk_last_rescan advance.
+ * How: the certified top-`depth` lists (k <= depth <= 64) stay on the device and are filtered there; every dst
+ * row outside a list ranks after every row in it, so a list that keeps k entries is the answer.  Only the rows
+ * that keep fewer go to an exact scan that knows the row's excluded set.  ALBEDO_UNSEEN_DEPTH in the environment
+ * (read per call, clamped to [k, 64]) overrides the default depth of 48; no result depends on it.  ALBEDO_TOPK_PASS and the
+ * free-memory cap split the src rows into passes as in als_recommend. */
+enum { ALS_EXCLUDE_RATINGS = 0, ALS_EXCLUDE_PAIRS = 1 };
+int als_recommend_unseen(als_ctx* ctx, int side, int32_t k,
+                         const int32_t* subset, int64_t n_subset,
+                         int32_t mode, int64_t n_excl,
+                         const int32_t* excl_src, const int32_t* excl_dst /* raw ids, mode ALS_EXCLUDE_PAIRS */,
+                         int32_t* src_ids_out, int32_t* dst_ids_out, float* scores_out);
+/* Counters of the last als_recommend_unseen call: out[0] = known src rows served, out[1] = rows the filter could
+ * not certify, which went to the exact scan, out[2] = list entries the filter removed, out[3] = dst rows the
+ * exact scan scored (out[3] < out[1]·n_dst: it pruned). */
+int als_recommend_unseen_stats(const als_ctx* ctx, int64_t* out4);
+/* Device time of the last als_recommend_unseen call from HIP events on the context's stream (ms): out[0] =
+ * exclusion map + sort (0 in ALS_EXCLUDE_RATINGS mode), out[1] = the top-`depth` lists (plan and passes),
+ * out[2] = filter, out[3] = exact scan with exclusions, out[4] = total. */
+int als_recommend_unseen_timing(const als_ctx* ctx, double* out5);
 /* RankingEvaluator (RankingEvaluator.scala:83-139) on the device, the albedo protocol of
  * ALSRecommenderBuilder.scala:92-104: actual lists = intoUserActualItems(user, item, key desc, k) of
  * the given (user, item, key) rows (key = starred_at; rank() <= k, collect_list, slice(0, k) = the
