@@ -67,6 +67,20 @@ class als_audit(C.Structure):
     ]
 
 
+class als_objective_t(C.Structure):
+    _fields_ = [
+        ("total", C.c_double),
+        ("all_pairs", C.c_double),
+        ("ratings", C.c_double),
+        ("reg_side", C.c_double),
+        ("reg_other", C.c_double),
+        ("sse", C.c_double),
+        ("abs_terms", C.c_double),
+        ("n_ratings", C.c_int64),
+        ("rows", C.c_int64),
+    ]
+
+
 class als_fold_params(C.Structure):
     _fields_ = [
         ("reg_param", C.c_double),
@@ -156,6 +170,9 @@ SIGNATURES = [
     ("als_path_stats", C.c_int, [P, C.c_int, I64P]),
     ("als_solver_stats", C.c_int, [P, C.c_int, I64P]),
     ("als_audit_rows", C.c_int, [P, C.c_int, C.c_double, F64P, C.POINTER(als_audit)]),
+    ("als_objective", C.c_int, [P, C.c_int, F64P, C.POINTER(als_objective_t)]),
+    ("als_objective_timing", C.c_int, [P, F64P]),
+    ("als_fit_tracked", C.c_int, [P, C.c_double, C.c_int32, F64P, I32P, I32P]),
     ("als_topk_stats", C.c_int, [P, I64P]),
     ("als_topk_timing", C.c_int, [P, F64P]),
     ("als_get_basis", C.c_int, [P, C.c_int, F64P]),
@@ -247,6 +264,19 @@ def fold_in(ctx, side, row_id, src_id, rating, rank, reg_param=None, alpha=None,
     if nr.value > cap:
         raise ValueError(f"fold_in: {nr.value} distinct row ids, cap {cap}")
     return ids[:nr.value].copy(), deg[:nr.value].copy(), fac[:nr.value].copy()
+
+
+def fit_tracked(ctx, max_iter, tol=None):
+    """als_fit_tracked on the context handle `ctx`: (objective history as a list of floats, entry 0 = after the
+    initialisation; sweeps run).  tol None: every sweep runs."""
+    import numpy as np
+
+    cap = int(max_iter) + 1
+    hist = np.empty(cap, dtype=np.float64)
+    n, ran = C.c_int32(0), C.c_int32(0)
+    check(load().als_fit_tracked(ctx, 0.0 if tol is None else float(tol), cap, ptr(hist, C.c_double), C.byref(n),
+                                 C.byref(ran)))
+    return hist[:n.value].tolist(), int(ran.value)
 
 
 def fold_in_timing(ctx):

@@ -164,7 +164,18 @@ class ALS(_Params):
                                            "No ratings available from the input dataset.")
         return np.ascontiguousarray(user), np.ascontiguousarray(item), rating
 
-    def fit(self, dataset, params=None, initialUserFactors=None, initialItemFactors=None, parallelism=8):
+    def _run_fit(self, h, pm, tracked, tol):
+        """als_fit, or als_fit_tracked when asked: (seconds, objective history or None, sweeps run or None)."""
+        t0 = time.perf_counter()
+        hist = ran = None
+        if tracked:
+            hist, ran = _lib.fit_tracked(h, int(pm["maxIter"]), tol)
+        else:
+            check(load().als_fit(h))
+        return time.perf_counter() - t0, hist, ran
+
+    def fit(self, dataset, params=None, initialUserFactors=None, initialItemFactors=None, parallelism=8,
+            trackObjective=False, tol=None):
         """ALS.fit (Spark Estimator.fit(dataset[, paramMap | paramMaps])).
 
         `params` = one ParamMap (dict) -> one ALSModel fitted with those overrides; a list of ParamMaps
@@ -173,9 +184,18 @@ class ALS(_Params):
         rank-dependent buffers are rebuilt (als_set_params).  The column names must agree across the
         maps.  `initial*Factors` = (ids, factors[n, rank]) injects the start point (parity path, one
         map only); without it the Spark-style XORShiftRandom initialisation is used.  `parallelism`
-        (the name of Spark 2.3's CrossValidator knob) caps the maps of a list fitted at once."""
+        (the name of Spark 2.3's CrossValidator knob) caps the maps of a list fitted at once.
+
+        `trackObjective` / `tol` (arguments of this call, not Params): with either, the fit evaluates the
+        training loss (ALSModel.objective, als_objective) after the initialisation and after every sweep;
+        the model carries `objectiveHistory` (a list of floats, entry 0 = after the initialisation) and
+        `sweepsRun`.  tol > 0 stops the fit after the first sweep whose relative decrease of the loss is
+        below tol; the factors are those of a fit with maxIter = sweepsRun.  In a list of ParamMaps every
+        map is fitted the same way.  Without either the fit is als_fit and the two attributes are None."""
+        tracked = bool(trackObjective) or tol is not None
         if isinstance(params, (list, tuple)):
-            return self._fit_many(dataset, [self._param_map(pm) for pm in params], max_concurrent=parallelism)
+            return self._fit_many(dataset, [self._param_map(pm) for pm in params], max_concurrent=parallelism,
+                                  tracked=tracked, tol=tol)
         pm = self._param_map(params or {})
         user, item, rating = self._ratings(dataset, pm)
         lib = load()
@@ -188,17 +208,16 @@ class ALS(_Params):
                     ids = np.ascontiguousarray(init[0], dtype=np.int32)
                     f = np.ascontiguousarray(init[1], dtype=np.float32)
                     check(lib.als_set_initial_factors(h, side, ids.size, ptr(ids, C.c_int32), ptr(f, C.c_float)))
-            t0 = time.perf_counter()
-            check(lib.als_fit(h))
-            fit_s = time.perf_counter() - t0
+            fit_s, hist, ran = self._run_fit(h, pm, tracked, tol)
         except Exception:
             lib.als_destroy(h)
             raise
         model = ALSModel(h, pm, uid=self.uid)
         model.fit_seconds = fit_s
+        model.objectiveHistory, model.sweepsRun = hist, ran
         return model
 
-    def _fit_many(self, dataset, maps, max_concurrent=8):
+    def _fit_many(self, dataset, maps, max_concurrent=8, tracked=False, tol=None):
         """The CV grid (ALSRecommenderCV.scala:67-90): one ingest; the maps of one rank are fitted
         CONCURRENTLY, each on an als_fork of the ingest context (own factors and streams, shared CSR)
         driven by its own host thread; every model is bit-identical to its standalone fit.
@@ -219,10 +238,8 @@ class ALS(_Params):
         h = self._context(maps[0])
         models = [None] * len(maps)
 
-        def run(fh):
-            t0 = time.perf_counter()
-            check(lib.als_fit(fh))
-            return time.perf_counter() - t0
+        def run(fh, pm):
+            return self._run_fit(fh, pm, tracked, tol)
 
         def oom(e):
             return isinstance(e, _lib.ALSError) and e.code == _lib.ALS_E_OUT_OF_MEMORY
@@ -253,12 +270,14 @@ class ALS(_Params):
                                 break  # fit the forks that fit in memory first
                             forks.append((i, fh))
                         with ThreadPoolExecutor(max_workers=len(forks)) as ex:
-                            futs = [ex.submit(run, fh) for _, fh in forks]
+                            futs = [ex.submit(run, fh, maps[i]) for i, fh in forks]
                         done, failed = [], []
                         for (i, fh), fu in zip(forks, futs):
                             e = fu.exception()
                             if e is None:
-                                models[i] = self._snapshot(fh, maps[i], fu.result())
+                                fit_s, hist, ran = fu.result()
+                                models[i] = self._snapshot(fh, maps[i], fit_s)
+                                models[i].objectiveHistory, models[i].sweepsRun = hist, ran
                                 done.append(i)
                             elif oom(e) and len(forks) > 1:
                                 failed.append(i)
@@ -304,6 +323,8 @@ class ALSModel(_Params):
         self._h = handle
         self._cache = {}
         self._loaded = False  # ALSModel.load: the estimator's params are not known
+        self.objectiveHistory = None  # ALS.fit(trackObjective=True / tol=...): the loss per sweep, entry 0 = the start
+        self.sweepsRun = None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -609,6 +630,28 @@ class ALSModel(_Params):
         out = {name: getattr(a, name) for name, _ in _lib.als_audit._fields_}
         out["worst_path"] = _lib.PATH_NAMES[a.worst_path] if a.worst_path >= 0 else None
         return (out, eta) if per_row else out
+
+    def objective(self, side="user", per_row=False):
+        """als_objective: the loss ALS minimises, in fp64 on the device, walked through the rows of `side`.
+
+        Returns a dict of als_objective_t's fields (total, all_pairs, ratings, reg_side, reg_other, sse,
+        abs_terms, n_ratings, rows) with `rmse` = sqrt(sse / n_ratings) and, with per_row, each row's loss in
+        ascending id order.  Needs the ratings, like audit: a loaded model or one of a ParamMap list raises
+        IllegalStateException."""
+        lib = load()
+        side = self._side(side)
+        o = _lib.als_objective_t()
+        loss = np.empty(max(int(lib.als_num_rows(self._h, side)), 0), np.float64) if per_row else None
+        check(lib.als_objective(self._h, side, ptr(loss, C.c_double) if per_row else None, C.byref(o)))
+        out = {name: getattr(o, name) for name, _ in _lib.als_objective_t._fields_}
+        out["rmse"] = float(np.sqrt(o.sse / o.n_ratings)) if o.n_ratings > 0 else float("nan")
+        return (out, loss) if per_row else out
+
+    def objective_timing(self):
+        """Device ms of the last objective call: the fp64 Gram, the row pass and the sums, total."""
+        out = np.zeros(3, np.float64)
+        check(load().als_objective_timing(self._h, ptr(out, C.c_double)))
+        return dict(zip(("gram", "rows", "total"), out.tolist()))
 
     # ---- fold-in: factors for rows the fit did not see (als_fold_in) ---------------------------------
     def _fold_params(self, regParam, alpha, implicitPrefs, nonnegative=None):

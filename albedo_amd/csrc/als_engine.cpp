@@ -657,6 +657,30 @@ int als_fit(als_ctx* c) {
   return als_run_sweeps(c, c->p.max_iter);
 }
 
+int als_fit_tracked(als_ctx* c, double tol, int32_t cap, double* history_out, int32_t* n_history_out,
+                    int32_t* sweeps_run_out) {
+  if (!c || !n_history_out || !sweeps_run_out) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
+  if (!c->has_ratings)
+    return fail(ALS_E_INVALID_ARGUMENT, "No ratings available from the input dataset (empty ratings).");
+  TRYC(objective_ready(c, "als_fit_tracked"));
+  TRYC(set_device(c));
+  TRYC(spark_init(c));  // only the sides the caller did not inject
+  std::vector<double> hist;
+  als_objective_t o{};
+  TRYC(objective(c, ALS_USER, nullptr, &o));
+  hist.push_back(o.total);
+  for (int s = 1; s <= c->p.max_iter; ++s) {
+    TRYC(als_run_sweeps(c, 1));
+    TRYC(objective(c, ALS_USER, nullptr, &o));
+    hist.push_back(o.total);
+    if (tol > 0.0 && hist[s - 1] - hist[s] < tol * std::fabs(hist[s - 1])) break;  // false for a NaN: the fit runs on
+  }
+  *sweeps_run_out = (int32_t)hist.size() - 1;
+  *n_history_out = (int32_t)hist.size();
+  if (history_out && (int64_t)hist.size() <= (int64_t)cap) std::copy(hist.begin(), hist.end(), history_out);
+  return ALS_OK;
+}
+
 int als_get_basis(als_ctx* c, int side, double* out) {
   if (!c || (side != 0 && side != 1) || !out) return fail(ALS_E_INVALID_ARGUMENT, "bad args");
   const Side& S = c->s[side];

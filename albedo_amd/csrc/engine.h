@@ -1,6 +1,6 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking; audit_host.cpp: the row audit; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation; query_topk_host.cpp:
+// held-out pair ranking; audit_host.cpp: the row audit; objective_host.cpp: the training loss; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation; query_topk_host.cpp:
 // top-k of caller-supplied vectors): error reporting, the device buffer, the row buckets, the per-side state, the
 // context and the few functions one file calls in another.  Not part of the public C ABI
 // (include/albedo_als.h).
@@ -227,6 +227,8 @@ struct als_ctx {
   int64_t fold_stats[4] = {0, 0, 0, 0};
   // device time of the last als_explain call (ms): map + sort + CSR of triples and pairs, src Gram, solve, total
   double explain_ms[4] = {0, 0, 0, 0};
+  // device time of the last als_objective call (ms): src Gram, row pass + sums, total
+  double objective_ms[3] = {0, 0, 0};
   // device time of the last als_recommend_vectors call (ms): exclusion map + sort, scan, merge, total
   double query_ms[4] = {0, 0, 0, 0};
   // the last als_recommend_unseen call: known src rows served, rows sent to the exact scan, list entries the
@@ -286,6 +288,12 @@ int original_rows(als_ctx* c, int side, DevBuf* own, DevBuf* padded);
 int64_t find_row(const Side& S, int32_t id);  // dense row of a raw id, -1 when unknown
 // all-gather of host blocks: buf holds world blocks of n floats (this rank's filled)
 int allgather_host(als_ctx* c, float* buf, int64_t n);
+
+// ---- objective_host.cpp --------------------------------------------------------------------------
+// ALS_E_STATE without ratings, ALS_E_UNSUPPORTED for world > 1; `who` names the caller in the message
+int objective_ready(const als_ctx* c, const char* who);
+// als_objective behind its argument checks: dst side t, both sides hold factors, the device is set
+int objective(als_ctx* c, int t, double* row_loss_out, als_objective_t* out);
 
 // ---- sweep_host.cpp ------------------------------------------------------------------------------
 // Everything that depends on the rank / light-row limit rather than on the ratings: degree buckets,

@@ -353,6 +353,41 @@ hipError_t launch_audit_rows(int KP, const AuditArgs& g, int64_t l0, int64_t n_l
 hipError_t launch_audit_summary(const double* eta, const int32_t* neg, int64_t n, double tol, AuditSummary* part,
                                 AuditSummary* out, hipStream_t s);
 
+// ---- objective (objective.hip): the loss ALS minimises, per dst row and summed (als_objective) ---------
+// A dst row's record, OBJ_REC doubles: the columns launch_objective_colsum adds
+enum { OBJ_ALL_PAIRS = 0, OBJ_RATINGS, OBJ_REG, OBJ_SSE, OBJ_ABS, OBJ_DEGREE, OBJ_LOSS, OBJ_REC = 8 };
+constexpr int OBJ_CHUNK_REC = 4;       // a chunk's record: Σ t, Σ (r − s)², Σ |terms|, n
+constexpr int OBJ_SUM_BLOCKS = 1024;   // rows of launch_objective_colsum's first pass (`part`)
+struct ObjectiveArgs {
+  const float* Y;            // src factors in the original basis, [*][KP], indexed by col
+  const float* X;            // dst rows in the original basis, [n rows][KP]
+  const int64_t* ptr;        // dst CSR
+  const int32_t* col;
+  const float* val;
+  const double* G;           // fp64 src Gram [KP][KP] (implicit), null when explicit
+  double* GX;                // scratch [nb][KP]: G·x of the batch's rows; null when explicit
+  int64_t row0, nb;          // the batch: rows [row0, row0 + nb)
+  int implicit;
+  double alpha, reg;
+  int64_t chunk;             // rows of more ratings are cut into chunks of this many
+  const int32_t* chunk_row;  // [n_chunks] dst row of each chunk, rows ascending, a row's chunks in order
+  const int32_t* chunk_idx;  // [n_chunks] chunk number within its row
+  int64_t n_chunks;
+  const int32_t* long_row;   // [n_long] the rows above `chunk`, ascending
+  const int64_t* long_slot0; // [n_long + 1] first chunk of each
+  double* partial;           // [n_chunks][OBJ_CHUNK_REC]
+  double* rec;               // out [n rows][OBJ_REC]
+};
+// the partial records of every chunk of the long rows (once per call, before the batches)
+hipError_t launch_objective_chunks(int KP, const ObjectiveArgs& g, hipStream_t s);
+// one batch: G·x, the rows of at most `chunk` ratings, then the long rows [l0, l0 + n_long) of the list
+hipError_t launch_objective_rows(int KP, const ObjectiveArgs& g, int64_t l0, int64_t n_long, hipStream_t s);
+// out[i] = n_i·‖y_i‖² over the n rows of a side from its own CSR: n_i = ratings > 0 (val null: the degree)
+hipError_t launch_objective_other(int KP, const float* Y, const int64_t* ptr, const float* val, int64_t n, double* out,
+                                  hipStream_t s);
+// out[w] = Σ_i in[i][w] over the n rows of in [n][W] (W <= OBJ_REC) in a fixed order; part: OBJ_SUM_BLOCKS·W doubles
+hipError_t launch_objective_colsum(const double* in, int64_t n, int W, double* part, double* out, hipStream_t s);
+
 // ---- fold-in (foldin.hip): factors of new rows from the frozen other side (als_fold_in) ----------------
 constexpr int FOLD_TILE = 32;  // ratings gathered into LDS per build step
 // The triples as a CSR over the distinct row ids.  Sort key: the row id (sign bit flipped) above the src

@@ -458,6 +458,55 @@ typedef struct als_audit {
  * one wave's share of the ratings, at least 512) are summed in chunks, in chunk order. */
 int als_audit_rows(als_ctx* ctx, int dst_side, double tol, double* eta_out /* [als_num_rows] or NULL */,
                    als_audit* out);
+/* The loss that ALS minimises, in fp64 on the device, from the current factors of both sides in the original
+ * basis (what als_get_factors returns) and the fp32 ratings.  Per rating r of row j of `side` on row i of the
+ * other side, s = x_j·y_i; with c, w, n_j and G as als_audit_rows defines them for implicitPrefs (c = alpha·|r|,
+ * w = (r > 0 ? 1 + c : 0), n_j = the count of r > 0, G = the fp64 Gram of all rows of the other side), and
+ * n_j = the degree, G = 0 otherwise:
+ *   implicit:  t_r = c·s^2 - 2·w·s + w          explicit:  t_r = (r - s)^2
+ *   loss_j = x_j^T G x_j + sum_{r in row j} t_r + regParam·n_j·|x_j|^2
+ *   total  = sum_j loss_j + regParam·sum_i n_i·|y_i|^2,          n_i from the other side's own rows.
+ * With implicitPrefs sum_j (x_j^T G x_j + sum t_r) is the sum over ALL pairs (j, i) of conf·(p - x_j·y_i)^2,
+ * conf = 1 + c on rated pairs and 1 elsewhere, p = [r > 0]: the cost of Hu, Koren and Volinsky with Spark's
+ * weighted regulariser, the function whose gradient per row is the normal equation of als_fold_in and
+ * als_audit_rows.  Every half-sweep minimises it over one side, so it falls after each.  A copy of a pair
+ * counts once per copy, a zero rating adds nothing to t but is a rated pair, a negative rating adds c·s^2.
+ * `side` chooses the CSR that is walked and the rows of row_loss_out ([als_num_rows(side)], ascending ids, or
+ * NULL); the total is the same from either side up to rounding.  sse / n_ratings is the squared training RMSE.
+ * abs_terms is the sum of the absolute values of everything added and so the scale of the rounding error.
+ * Two calls give identical bits; no floating-point atomics are used, rows and chunks are added in a fixed
+ * order.  Rows longer than ALBEDO_OBJECTIVE_CHUNK ratings (environment, read per call; default as
+ * ALBEDO_AUDIT_CHUNK) are summed in chunks, in chunk order; the value changes the result by rounding only.
+ * The model is read-only: factors, bases, Gram caches, sweep timings, path stats, top-k counters and the
+ * fold-in / explain timings are unchanged, and a call between two half-sweeps leaves the fit bit-identical.
+ * Non-finite factors give non-finite outputs and are not an error.  Forks may call it.  ALS_E_STATE without
+ * ratings (contexts from als_model_create) or when a side has no factors; ALS_E_INVALID_ARGUMENT for a bad
+ * side or a null out; ALS_E_UNSUPPORTED for world > 1. */
+typedef struct als_objective_t {
+  double total;       /* all_pairs + ratings + reg_side + reg_other */
+  double all_pairs;   /* sum_j x_j^T G x_j   (0 for explicit) */
+  double ratings;     /* sum_r t_r */
+  double reg_side;    /* regParam·sum_j n_j |x_j|^2 over `side` */
+  double reg_other;   /* the same over the other side */
+  double sse;         /* sum_r (r - s_r)^2: training RMSE = sqrt(sse / n_ratings); equals `ratings` when explicit */
+  double abs_terms;   /* sum of the absolute values of everything added: |x_j^T G x_j| + sum_r (|c s^2| + |2 w s|
+                         + |w|) (explicit: t_r) + both reg terms */
+  int64_t n_ratings, rows;
+} als_objective_t;
+int als_objective(als_ctx* ctx, int side, double* row_loss_out /* [als_num_rows(side)] or NULL */,
+                  als_objective_t* out);
+/* Device time of the last als_objective call from HIP events on the context's stream (ms): out[0] = the fp64
+ * Gram (0 for explicit), out[1] = the row pass and the sums, out[2] = total. */
+int als_objective_timing(const als_ctx* ctx, double* out3);
+/* als_fit with the objective (als_objective through the user-side CSR, `total`) evaluated after the
+ * initialisation, history[0], and after every full sweep s, history[s].  tol > 0: the fit stops after the first
+ * sweep s >= 1 with history[s-1] - history[s] < tol·|history[s-1]| (an increase stops it; a NaN never satisfies
+ * the test, so the fit runs on).  tol <= 0 or NaN: all max_iter sweeps run.  *sweeps_run_out = the sweeps run,
+ * *n_history_out = that + 1; history_out is filled when non-null and *n_history_out <= cap (cap = max_iter + 1
+ * always suffices).  The factors after s sweeps are bit-identical to als_fit with max_iter = s.  Errors as
+ * als_fit, and ALS_E_UNSUPPORTED for world > 1. */
+int als_fit_tracked(als_ctx* ctx, double tol, int32_t cap, double* history_out /* [cap] */,
+                    int32_t* n_history_out, int32_t* sweeps_run_out);
 /* Top-k counters since als_create (als_recommend with k <= 64): out[0] = src rows through the MFMA
  * scan, out[1] = rows whose candidate set failed certification and were re-scored by the exact scan,
  * out[2] = dst rows the scan waves scored (a wave skips a chunk none of its rows can use), out[3] = the same without the chunk
