@@ -2,12 +2,12 @@
 // into the original basis, forms the fp64 src Gram, runs the audit kernels over the dst rows in batches
 // and reads back the summary (and the per-row values when asked).  It uses nothing a half-sweep left
 // behind except the factors and their bases; every buffer but the context's Gram (d_G, which the
-// all-reduce works on and every half-sweep rewrites) is owned by the call.
+// all-reduce works on and every half-sweep rewrites) is owned by the call, and a guard declared after
+// them drains the stream on every return.  The chunk plan and the batches are row_plan.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <limits>
 #include <string>
 #include <vector>
@@ -15,24 +15,11 @@
 #include "albedo_als.h"
 #include "engine.h"
 #include "kernels.h"
+#include "row_plan.h"
 
 using namespace albedo;
 
 namespace {
-
-// Ratings per chunk of a long row.  A row is one wave's work, so a launch runs as long as its longest
-// row; the rule for skewed gathers is to cut lists longer than a quarter of one wave's share of the
-// work (ratings / waves in flight) into chunks of that size.  The waves are counted at the hardware's 8
-// per SIMD, more than the row kernel's registers allow: the smaller share errs towards more chunks,
-// which cost one record each.  512, the size that rule was measured at, is the floor: below it a chunk
-// record (2·KP + 2 doubles) stops being small beside the gather it stands for.  ALBEDO_AUDIT_CHUNK
-// overrides it (tests: 256).
-int64_t audit_chunk_len(const als_ctx* c, int64_t own_nnz) {
-  const char* e = std::getenv("ALBEDO_AUDIT_CHUNK");
-  if (e && *e && std::atoll(e) > 0) return std::atoll(e);
-  const int64_t waves = (int64_t)c->n_cu * 4 * 8;
-  return std::max<int64_t>(512, own_nnz / (4 * waves));
-}
 
 int audit(als_ctx* c, int t, double tol, double* eta_out, als_audit* out) {
   Side& S = c->s[1 - t];
@@ -40,8 +27,10 @@ int audit(als_ctx* c, int t, double tol, double* eta_out, als_audit* out) {
   const int KP = c->KP;
   hipStream_t st = c->st;
   if (c->world > 1) TRYC(drain(c));
+  DevBuf own_s, padded_s, own_t, slab, gx, d_eta, d_neg, d_sum;
+  RowPlan plan;
+  Drain queued{st};
   // both sides in the original basis: Y as the CSR's col indexes it, X by own row
-  DevBuf own_s, padded_s, own_t;
   const float *Y, *Yown, *X;
   if (c->world == 1) {
     TRYC(materialize(c, 1 - t));
@@ -65,8 +54,7 @@ int audit(als_ctx* c, int t, double tol, double* eta_out, als_audit* out) {
   g.nonneg = c->p.nonnegative;
   g.alpha = c->p.alpha;
   g.reg = c->p.reg_param;
-  DevBuf slab, gx;
-  const int64_t batch = std::max<int64_t>(64, std::min<int64_t>(T.own_n, ((int64_t)256 << 20) / (KP * 8)));
+  const int64_t batch = row_batch_len(T.own_n, KP);
   if (c->p.implicit_prefs) {
     const int nblk = audit_gram_blocks(S.own_n);
     HIPCHK(slab.ensure((size_t)nblk * KP * KP * 8));
@@ -81,70 +69,24 @@ int audit(als_ctx* c, int t, double tol, double* eta_out, als_audit* out) {
     HIPCHK(gx.ensure((size_t)batch * KP * 8));
     g.GX = gx.as<double>();
   }
-  // long rows and their chunks, rows ascending
-  g.chunk = audit_chunk_len(c, T.own_nnz);
-  std::vector<int32_t> crow, cidx, lrow;
-  std::vector<int64_t> slot0{0};
-  for (int64_t r = 0; r < T.own_n; ++r) {
-    if (T.h_deg[r] <= g.chunk) continue;
-    const int64_t nch = (T.h_deg[r] + g.chunk - 1) / g.chunk;
-    for (int64_t k = 0; k < nch; ++k) {
-      crow.push_back((int32_t)r);
-      cidx.push_back((int32_t)k);
-    }
-    lrow.push_back((int32_t)r);
-    slot0.push_back((int64_t)crow.size());
-  }
-  DevBuf d_crow, d_cidx, d_lrow, d_slot0, d_partial, d_eta, d_neg, d_sum;
-  g.n_chunks = (int64_t)crow.size();
-  if (g.n_chunks > 0) {
-    HIPCHK(d_crow.ensure(crow.size() * 4));
-    HIPCHK(d_cidx.ensure(cidx.size() * 4));
-    HIPCHK(d_lrow.ensure(lrow.size() * 4));
-    HIPCHK(d_slot0.ensure(slot0.size() * 8));
-    HIPCHK(d_partial.ensure(crow.size() * (size_t)(2 * KP + 2) * 8));
-    HIPCHK(copy_st(c, d_crow.p, crow.data(), crow.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_cidx.p, cidx.data(), cidx.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_lrow.p, lrow.data(), lrow.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_slot0.p, slot0.data(), slot0.size() * 8, hipMemcpyHostToDevice));
-    g.chunk_row = d_crow.as<int32_t>();
-    g.chunk_idx = d_cidx.as<int32_t>();
-    g.long_row = d_lrow.as<int32_t>();
-    g.long_slot0 = d_slot0.as<int64_t>();
-    g.partial = d_partial.as<double>();
-  }
+  g.chunk = row_chunk_len(c, T.own_nnz, "ALBEDO_AUDIT_CHUNK");
+  TRYC(plan.build(c, T, 2 * KP + 2, &g));
   HIPCHK(d_eta.ensure((size_t)std::max<int64_t>(T.own_n, 1) * 8));
   HIPCHK(d_neg.ensure((size_t)std::max<int64_t>(T.own_n, 1) * 4));
   HIPCHK(d_sum.ensure((size_t)(AUDIT_SUM_BLOCKS + 1) * sizeof(AuditSummary)));
   g.eta = d_eta.as<double>();
   g.neg = d_neg.as<int32_t>();
-  // From here to the synchronisation below the kernels read the call's buffers: a failed launch waits
-  // for the queued ones before the buffers go
-  auto run = [&]() -> int {
-    HIPCHK(launch_audit_chunks(KP, g, st));
-    int64_t l0 = 0;
-    for (int64_t r0 = 0; r0 < T.own_n; r0 += batch) {
-      g.row0 = r0;
-      g.nb = std::min<int64_t>(batch, T.own_n - r0);
-      int64_t l1 = l0;
-      while (l1 < (int64_t)lrow.size() && lrow[l1] < r0 + g.nb) ++l1;
-      HIPCHK(launch_audit_rows(KP, g, l0, l1 - l0, st));
-      l0 = l1;
-    }
-    AuditSummary* part = d_sum.as<AuditSummary>();
-    HIPCHK(launch_audit_summary(g.eta, g.neg, T.own_n, tol, part + 1, part, st));
+  HIPCHK(launch_audit_chunks(KP, g, st));
+  TRYC(plan.batches(T.own_n, batch, [&](int64_t row0, int64_t nb, int64_t l0, int64_t n_long) -> int {
+    g.row0 = row0;
+    g.nb = nb;
+    HIPCHK(launch_audit_rows(KP, g, l0, n_long, st));
     return ALS_OK;
-  };
+  }));
+  AuditSummary* part = d_sum.as<AuditSummary>();
+  HIPCHK(launch_audit_summary(g.eta, g.neg, T.own_n, tol, part + 1, part, st));
   AuditSummary sum{};
-  int rc = run();
-  if (rc == ALS_OK) {
-    const hipError_t e = copy_st(c, &sum, d_sum.p, sizeof sum, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(ALS_E_HIP, std::string("HIP error: ") + hipGetErrorString(e) + " in the row audit");
-  }
-  if (rc != ALS_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
+  HIPCHK(copy_st(c, &sum, d_sum.p, sizeof sum, hipMemcpyDeviceToHost));
   if (eta_out) {
     std::fill(eta_out, eta_out + T.n, std::numeric_limits<double>::quiet_NaN());
     HIPCHK(copy_st(c, eta_out + T.own0, d_eta.p, (size_t)T.own_n * 8, hipMemcpyDeviceToHost));

@@ -1,9 +1,10 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
-// held-out pair ranking; audit_host.cpp: the row audit; objective_host.cpp: the training loss; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation; query_topk_host.cpp:
-// top-k of caller-supplied vectors): error reporting, the device buffer, the row buckets, the per-side state, the
-// context and the few functions one file calls in another.  Not part of the public C ABI
-// (include/albedo_als.h).
+// held-out pair ranking; audit_host.cpp: the row audit; objective_host.cpp: the training loss, both
+// over row_plan.h; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation;
+// query_topk_host.cpp: top-k of caller-supplied vectors): error reporting, the device buffer, the
+// stream guards, the row buckets, the per-side state, the context and the few functions one file calls
+// in another.  Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -99,6 +100,32 @@ struct Event {
   void reset() {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
+  }
+};
+
+// Declared after the buffers a call queues work on, so that it goes first: whatever way the call
+// returns, a failed launch included, the stream is drained before a buffer is freed
+struct Drain {
+  hipStream_t s;
+  ~Drain() {
+    if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+template <int N>
+struct Marks {  // stage marks on the stream
+  hipEvent_t e[N] = {};
+  Marks() = default;
+  Marks(const Marks&) = delete;
+  Marks& operator=(const Marks&) = delete;
+  ~Marks() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t mark(int i, hipStream_t s) {
+    hipError_t r = hipEventCreate(&e[i]);
+    if (r != hipSuccess) return r;
+    return hipEventRecord(e[i], s);
   }
 };
 

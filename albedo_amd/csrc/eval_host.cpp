@@ -18,15 +18,6 @@
 namespace albedo {
 namespace {
 
-// Declared after the buffers a call queues work on, so that it goes first: whatever way the call
-// returns, the stream is drained before a buffer is freed.
-struct Drain {
-  hipStream_t s;
-  ~Drain() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
 // Stage marks on the stream: ms[i] = device time between mark i and mark i + 1
 struct StageClock {
   hipEvent_t e[6] = {};

@@ -21,31 +21,6 @@ using namespace albedo;
 
 namespace {
 
-// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
-// the queued ones before the buffers go
-struct Drain {
-  hipStream_t s;
-  ~Drain() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
-struct Marks {  // stage marks on the stream
-  hipEvent_t e[4] = {};
-  Marks() = default;
-  Marks(const Marks&) = delete;
-  Marks& operator=(const Marks&) = delete;
-  ~Marks() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t mark(int i, hipStream_t s) {
-    hipError_t r = hipEventCreate(&e[i]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[i], s);
-  }
-};
-
 // what a pair that cannot be explained gets, and the whole answer when there are no triples
 void fill_unexplained(int64_t n_pairs, int32_t m, double* total, int32_t* ids, double* contrib) {
   const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -65,7 +40,7 @@ int explain(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad;
   DevBuf p_row, p_tgt, p_key, p_keys, p_target, p_hi, p_slot, p_runs, p_cnt, p_ptr, p_nr, p_deg, p_degs, p_iota, p_order;
   DevBuf d_total, d_oids, d_contrib;
-  Marks clk;
+  Marks<4> clk;
   Drain queued{st};
   for (DevBuf* b : {&d_row, &d_src, &d_val, &d_vals, &d_hi, &d_col, &d_runs, &d_ids, &d_deg, &d_degs, &d_iota, &d_order})
     HIPCHK(b->ensure((size_t)n * 4));

@@ -21,31 +21,6 @@ using namespace albedo;
 
 namespace {
 
-// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
-// the queued ones before the buffers go
-struct Drain {
-  hipStream_t s;
-  ~Drain() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
-struct Marks {  // stage marks on the stream
-  hipEvent_t e[4] = {};
-  Marks() = default;
-  Marks(const Marks&) = delete;
-  Marks& operator=(const Marks&) = delete;
-  ~Marks() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t mark(int i, hipStream_t s) {
-    hipError_t r = hipEventCreate(&e[i]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[i], s);
-  }
-};
-
 int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int nonneg, int64_t n, const int32_t* row_id,
             const int32_t* src_id, const float* rating, int64_t cap, int64_t* n_rows_out, int32_t* ids_out,
             int64_t* degree_out, float* factors_out) {
@@ -55,7 +30,7 @@ int fold_in(als_ctx* c, int side, double reg, double alpha, int implicit, int no
   TRYC(materialize(c, 1 - side));
   DevBuf d_row, d_src, d_val, d_sids, d_key, d_keys, d_vals, d_hi, d_col, d_runs, d_cnt, d_ptr, d_nr, d_ids, d_deg, d_degs;
   DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad, d_stats, d_X;
-  Marks clk;
+  Marks<4> clk;
   Drain queued{st};
   for (DevBuf* b : {&d_row, &d_src, &d_val, &d_vals, &d_hi, &d_col, &d_runs, &d_ids, &d_deg, &d_degs, &d_iota, &d_order})
     HIPCHK(b->ensure((size_t)n * 4));

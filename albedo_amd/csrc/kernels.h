@@ -1,6 +1,6 @@
 // Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
-// eval_host.cpp, audit_host.cpp, foldin_host.cpp, query_topk_host.cpp) and the HIP kernels.
-// Not part of the public C ABI (include/albedo_als.h).
+// eval_host.cpp, audit_host.cpp and objective_host.cpp with row_plan.h, foldin_host.cpp, explain_host.cpp,
+// query_topk_host.cpp) and the HIP kernels.  Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -312,8 +312,8 @@ hipError_t eval_metric(int metric, const int32_t* pred, int pred_width, const in
 // *out = bits of max_r ||T[r][0..kreal)||_2 computed in fp64
 hipError_t launch_rownorm_max(const float* T, int64_t n, int KP, int kreal, unsigned long long* out, hipStream_t s);
 
-// ---- row audit (audit.hip): the fp64 normal-equation residual of every dst row (als_audit_rows) -------
-struct AuditArgs {
+// ---- the fp64 row pass (row_pass.h) under the row audit and the objective ------------------------------
+struct RowPassArgs {
   const float* Y;            // src factors in the original basis, [*][KP], indexed by col
   const float* X;            // dst rows in the original basis, [n rows][KP] (local row index, like ptr)
   const int64_t* ptr;        // dst CSR of the own rows
@@ -322,16 +322,24 @@ struct AuditArgs {
   const double* G;           // fp64 src Gram [KP][KP] (implicit), null when explicit
   double* GX;                // scratch [nb][KP]: G·x of the batch's rows; null when explicit
   int64_t row0, nb;          // the batch: rows [row0, row0 + nb)
-  int implicit, nonneg;
-  double alpha, reg;
-  double gnorm;              // ‖G‖_F (0 when explicit)
+  int implicit;
+  double alpha;
   int64_t chunk;             // rows of more ratings are cut into chunks of this many
   const int32_t* chunk_row;  // [n_chunks] dst row of each chunk, rows ascending, a row's chunks in order
   const int32_t* chunk_idx;  // [n_chunks] chunk number within its row
   int64_t n_chunks;
   const int32_t* long_row;   // [n_long] the rows above `chunk`, ascending
   const int64_t* long_slot0; // [n_long + 1] first chunk of each
-  double* partial;           // [n_chunks][2·KP + 2] chunk records: Σ c (y·x) y, Σ w y, Σ c ‖y‖², n
+  double* partial;           // [n_chunks] chunk records of the pass's size
+};
+// GX[r] = G·X[row0 + r] for r < nb in fp64 (audit.hip, beside the fp64 Gram)
+hipError_t launch_row_gx(int KP, const float* X, const double* G, double* GX, int64_t row0, int64_t nb, hipStream_t s);
+
+// ---- row audit (audit.hip): the fp64 normal-equation residual of every dst row (als_audit_rows) -------
+struct AuditArgs : RowPassArgs {  // partial: [n_chunks][2·KP + 2], Σ c (y·x) y, Σ w y, Σ c ‖y‖², n
+  double reg;
+  int nonneg;
+  double gnorm;              // ‖G‖_F (0 when explicit)
   double* eta;               // out [n rows]
   int32_t* neg;              // out [n rows]: nonneg and a component of x below zero
 };
@@ -358,24 +366,8 @@ hipError_t launch_audit_summary(const double* eta, const int32_t* neg, int64_t n
 enum { OBJ_ALL_PAIRS = 0, OBJ_RATINGS, OBJ_REG, OBJ_SSE, OBJ_ABS, OBJ_DEGREE, OBJ_LOSS, OBJ_REC = 8 };
 constexpr int OBJ_CHUNK_REC = 4;       // a chunk's record: Σ t, Σ (r − s)², Σ |terms|, n
 constexpr int OBJ_SUM_BLOCKS = 1024;   // rows of launch_objective_colsum's first pass (`part`)
-struct ObjectiveArgs {
-  const float* Y;            // src factors in the original basis, [*][KP], indexed by col
-  const float* X;            // dst rows in the original basis, [n rows][KP]
-  const int64_t* ptr;        // dst CSR
-  const int32_t* col;
-  const float* val;
-  const double* G;           // fp64 src Gram [KP][KP] (implicit), null when explicit
-  double* GX;                // scratch [nb][KP]: G·x of the batch's rows; null when explicit
-  int64_t row0, nb;          // the batch: rows [row0, row0 + nb)
-  int implicit;
-  double alpha, reg;
-  int64_t chunk;             // rows of more ratings are cut into chunks of this many
-  const int32_t* chunk_row;  // [n_chunks] dst row of each chunk, rows ascending, a row's chunks in order
-  const int32_t* chunk_idx;  // [n_chunks] chunk number within its row
-  int64_t n_chunks;
-  const int32_t* long_row;   // [n_long] the rows above `chunk`, ascending
-  const int64_t* long_slot0; // [n_long + 1] first chunk of each
-  double* partial;           // [n_chunks][OBJ_CHUNK_REC]
+struct ObjectiveArgs : RowPassArgs {  // partial: [n_chunks][OBJ_CHUNK_REC]
+  double reg;
   double* rec;               // out [n rows][OBJ_REC]
 };
 // the partial records of every chunk of the long rows (once per call, before the batches)

@@ -2,58 +2,21 @@
 // factors into the original basis, forms the fp64 src Gram (implicit prefs), runs the row kernels over
 // the dst rows in batches, adds the other side's regulariser from that side's own ratings and reads back
 // the sums (and the per-row losses when asked).  It reads the model and writes nothing of it; every
-// buffer, the Gram included, is owned by the call.
+// buffer, the Gram included, is owned by the call.  The chunk plan and the batches are row_plan.h's,
+// shared with the row audit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "albedo_als.h"
 #include "engine.h"
 #include "kernels.h"
+#include "row_plan.h"
 
 using namespace albedo;
-
-namespace {
-
-// Ratings per chunk of a long row: the row audit's rule (audit_host.cpp audit_chunk_len), a quarter of one
-// wave's share of the ratings and at least 512.  ALBEDO_OBJECTIVE_CHUNK overrides it (tests: 256).
-int64_t objective_chunk_len(const als_ctx* c, int64_t own_nnz) {
-  const char* e = std::getenv("ALBEDO_OBJECTIVE_CHUNK");
-  if (e && *e && std::atoll(e) > 0) return std::atoll(e);
-  const int64_t waves = (int64_t)c->n_cu * 4 * 8;
-  return std::max<int64_t>(512, own_nnz / (4 * waves));
-}
-
-// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
-// the queued kernels before the buffers go
-struct Drain {
-  hipStream_t s;
-  ~Drain() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
-struct Marks {  // stage marks on the stream
-  hipEvent_t e[3] = {};
-  Marks() = default;
-  Marks(const Marks&) = delete;
-  Marks& operator=(const Marks&) = delete;
-  ~Marks() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t mark(int i, hipStream_t s) {
-    hipError_t r = hipEventCreate(&e[i]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[i], s);
-  }
-};
-
-}  // namespace
 
 namespace albedo {
 
@@ -65,8 +28,9 @@ int objective(als_ctx* c, int t, double* row_loss_out, als_objective_t* out) {
   // both sides in the original basis: Y as the CSR's col indexes it (world = 1: the dense row), X by row
   TRYC(materialize(c, 1 - t));
   TRYC(materialize(c, t));
-  DevBuf slab, d_G, gx, d_crow, d_cidx, d_lrow, d_slot0, d_partial, d_rec, d_other, d_part, d_sum;
-  Marks clk;
+  DevBuf slab, d_G, gx, d_rec, d_other, d_part, d_sum;
+  RowPlan plan;
+  Marks<3> clk;
   Drain queued{st};
   ObjectiveArgs g{};
   g.Y = S.d_orig.as<float>();
@@ -77,7 +41,7 @@ int objective(als_ctx* c, int t, double* row_loss_out, als_objective_t* out) {
   g.implicit = c->p.implicit_prefs;
   g.alpha = c->p.alpha;
   g.reg = c->p.reg_param;
-  const int64_t batch = std::max<int64_t>(64, std::min<int64_t>(T.own_n, ((int64_t)256 << 20) / (KP * 8)));
+  const int64_t batch = row_batch_len(T.own_n, KP);
   HIPCHK(clk.mark(0, st));
   if (c->p.implicit_prefs) {  // into a buffer of the call: c->d_G belongs to the half-sweeps
     const int nblk = audit_gram_blocks(S.own_n);
@@ -89,52 +53,20 @@ int objective(als_ctx* c, int t, double* row_loss_out, als_objective_t* out) {
     g.GX = gx.as<double>();
   }
   HIPCHK(clk.mark(1, st));
-  // long rows and their chunks, rows ascending
-  g.chunk = objective_chunk_len(c, T.own_nnz);
-  std::vector<int32_t> crow, cidx, lrow;
-  std::vector<int64_t> slot0{0};
-  for (int64_t r = 0; r < T.own_n; ++r) {
-    if (T.h_deg[r] <= g.chunk) continue;
-    const int64_t nch = (T.h_deg[r] + g.chunk - 1) / g.chunk;
-    for (int64_t k = 0; k < nch; ++k) {
-      crow.push_back((int32_t)r);
-      cidx.push_back((int32_t)k);
-    }
-    lrow.push_back((int32_t)r);
-    slot0.push_back((int64_t)crow.size());
-  }
-  g.n_chunks = (int64_t)crow.size();
-  if (g.n_chunks > 0) {
-    HIPCHK(d_crow.ensure(crow.size() * 4));
-    HIPCHK(d_cidx.ensure(cidx.size() * 4));
-    HIPCHK(d_lrow.ensure(lrow.size() * 4));
-    HIPCHK(d_slot0.ensure(slot0.size() * 8));
-    HIPCHK(d_partial.ensure(crow.size() * (size_t)OBJ_CHUNK_REC * 8));
-    HIPCHK(copy_st(c, d_crow.p, crow.data(), crow.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_cidx.p, cidx.data(), cidx.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_lrow.p, lrow.data(), lrow.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_st(c, d_slot0.p, slot0.data(), slot0.size() * 8, hipMemcpyHostToDevice));
-    g.chunk_row = d_crow.as<int32_t>();
-    g.chunk_idx = d_cidx.as<int32_t>();
-    g.long_row = d_lrow.as<int32_t>();
-    g.long_slot0 = d_slot0.as<int64_t>();
-    g.partial = d_partial.as<double>();
-  }
+  g.chunk = row_chunk_len(c, T.own_nnz, "ALBEDO_OBJECTIVE_CHUNK");
+  TRYC(plan.build(c, T, OBJ_CHUNK_REC, &g));
   HIPCHK(d_rec.ensure((size_t)std::max<int64_t>(T.own_n, 1) * OBJ_REC * 8));
   HIPCHK(d_other.ensure((size_t)std::max<int64_t>(S.own_n, 1) * 8));
   HIPCHK(d_part.ensure((size_t)OBJ_SUM_BLOCKS * OBJ_REC * 8));
   HIPCHK(d_sum.ensure((size_t)(OBJ_REC + 1) * 8));
   g.rec = d_rec.as<double>();
   HIPCHK(launch_objective_chunks(KP, g, st));
-  int64_t l0 = 0;
-  for (int64_t r0 = 0; r0 < T.own_n; r0 += batch) {
-    g.row0 = r0;
-    g.nb = std::min<int64_t>(batch, T.own_n - r0);
-    int64_t l1 = l0;
-    while (l1 < (int64_t)lrow.size() && lrow[l1] < r0 + g.nb) ++l1;
-    HIPCHK(launch_objective_rows(KP, g, l0, l1 - l0, st));
-    l0 = l1;
-  }
+  TRYC(plan.batches(T.own_n, batch, [&](int64_t row0, int64_t nb, int64_t l0, int64_t n_long) -> int {
+    g.row0 = row0;
+    g.nb = nb;
+    HIPCHK(launch_objective_rows(KP, g, l0, n_long, st));
+    return ALS_OK;
+  }));
   // the other side's n_i ‖y_i‖² from its own rows, then the sums: the records' columns and that vector
   HIPCHK(launch_objective_other(KP, g.Y, S.d_ptr.as<int64_t>(), c->p.implicit_prefs ? S.d_val.as<float>() : nullptr,
                                 S.own_n, d_other.as<double>(), st));

@@ -18,31 +18,6 @@ using namespace albedo;
 
 namespace {
 
-// Declared after the buffers the call queues work on, so that it goes first: a failed launch waits for
-// the queued ones before the buffers go
-struct Drain {
-  hipStream_t s;
-  ~Drain() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
-struct Marks {  // stage marks on the stream
-  hipEvent_t e[4] = {};
-  Marks() = default;
-  Marks(const Marks&) = delete;
-  Marks& operator=(const Marks&) = delete;
-  ~Marks() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t mark(int i, hipStream_t s) {
-    hipError_t r = hipEventCreate(&e[i]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[i], s);
-  }
-};
-
 // ptr0: the exclusion ranges shifted to start at 0 ([n_q + 1]), empty when the call has none
 int recommend_vectors(als_ctx* c, int side, int k, int64_t n_q, const float* q, const std::vector<int64_t>& ptr0,
                       const int32_t* excl_ids, int32_t* ids_out, float* scores_out) {
@@ -53,7 +28,7 @@ int recommend_vectors(als_ctx* c, int side, int k, int64_t n_q, const float* q, 
   const int64_t n_e = ptr0.empty() ? 0 : ptr0.back();
   const QueryPlan plan = query_plan(S.n, n_q, c->n_cu);
   DevBuf d_q, d_ids, d_ptr, d_eid, d_key, d_keys, d_tmp, d_ps, d_pr, d_oi, d_os;
-  Marks clk;
+  Marks<4> clk;
   Drain queued{st};
   HIPCHK(d_q.ensure((size_t)n_q * rank * 4));
   HIPCHK(d_ids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));

@@ -132,12 +132,7 @@ int topk_plan(als_ctx* c, int src, int k, TopkPlan& P, const std::function<void(
     DevBuf d_nrm;
     HIPCHK(d_nrm.ensure(16));
     // d_nrm outlives the work queued on it: an early return drains the stream before it is freed
-    struct Drain {
-      hipStream_t s;
-      ~Drain() {
-        if (s) (void)hipStreamSynchronize(s);
-      }
-    } queued{c->st};
+    Drain queued{c->st};
     TRYC(topk_dst_gram(c, T, P, ev_gram));
     HIPCHK(launch_rownorm_max(T.d_orig.as<float>(), T.n, KP, c->p.rank, d_nrm.as<unsigned long long>(), c->st));
     HIPCHK(launch_rownorm_max(S.d_orig.as<float>(), S.n, KP, c->p.rank, d_nrm.as<unsigned long long>() + 1, c->st));
@@ -740,14 +735,6 @@ struct MarkList {
   }
 };
 
-// Declared after the buffers a call queues work on, so that it goes first
-struct DrainStream {
-  hipStream_t s;
-  ~DrainStream() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
 // The depth of the filter's lists: ALBEDO_UNSEEN_DEPTH, else 48, clamped to [k, TOPK_KC].  A tuning choice:
 // no result depends on it.  c2, all users, k = 30: the lists cost 9.7 ms of device time at 48 and 294 ms at
 // 64, where the running threshold sits at the last place of the 64-entry candidate lists (topk_threshold_rank)
@@ -794,7 +781,7 @@ int recommend_unseen(als_ctx* c, int src, int k, const int32_t* subset, int64_t 
   DevBuf d_es, d_ed, d_sids, d_key, d_keys, d_tmp, d_ptr, d_lid, d_lsc, d_flag, d_cnt, d_stat;
   MarkList clk;
   TopkOutput out(c, ids_out, scores_out, k, 0, out_pos, INT64_MAX);  // never pinned: the synchronous sink
-  DrainStream queued{st};
+  Drain queued{st};
   HIPCHK(clk.mark(st));  // 0
   TRYC(topk_plan(c, src, depth, P));
   HIPCHK(clk.mark(st));  // 1
