@@ -158,6 +158,10 @@ SIGNATURES = [
                                        I32P, F32P]),
     ("als_recommend_unseen_stats", C.c_int, [P, I64P]),
     ("als_recommend_unseen_timing", C.c_int, [P, F64P]),
+    ("als_similar", C.c_int, [P, C.c_int, C.c_int32, I32P, C.c_int64, I32P, I32P, F32P]),
+    ("als_similar_vectors", C.c_int, [P, C.c_int, C.c_int32, C.c_int64, F32P, I64P, I32P, I32P, F32P]),
+    ("als_similar_timing", C.c_int, [P, F64P]),
+    ("als_similar_stats", C.c_int, [P, I64P]),
     ("als_evaluate_ndcg", C.c_int, [P, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P, C.c_int64]),
     ("als_evaluate_ranking", C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, I32P, I32P, I64P, F64P, I64P, I32P, F64P,
                                        C.c_int64]),
@@ -384,4 +388,59 @@ def recommend_vectors_timing(ctx):
 
     out = np.zeros(4, dtype=np.float64)
     check(load().als_recommend_vectors_timing(ctx, ptr(out, C.c_double)))
+    return out
+
+
+def similar(ctx, side, k, subset=None):
+    """als_similar on the context handle `ctx`: (src ids [n], ids [n, k], scores [n, k]) of the cosine top-k of
+    the requested rows of `side` (every row when subset is None) among the other rows of that side."""
+    import numpy as np
+
+    lib = load()
+    if subset is not None:
+        sub = np.ascontiguousarray(subset, dtype=np.int32).reshape(-1)
+        n = int(sub.size)
+    else:
+        sub, n = None, int(lib.als_num_rows(ctx, side))
+    src = np.empty(n, dtype=np.int32)
+    ids = np.empty((n, max(int(k), 0)), dtype=np.int32)
+    sc = np.empty((n, max(int(k), 0)), dtype=np.float32)
+    check(lib.als_similar(ctx, side, int(k), ptr(sub, C.c_int32) if sub is not None else None, n,
+                          ptr(src, C.c_int32), ptr(ids, C.c_int32), ptr(sc, C.c_float)))
+    return src, ids, sc
+
+
+def similar_vectors(ctx, side, vectors, k, rank, exclude=None):
+    """als_similar_vectors: recommend_vectors with the cosine of the query and each row of `side` as the score."""
+    import numpy as np
+
+    q = np.ascontiguousarray(vectors, dtype=np.float32)
+    if q.ndim != 2 or q.shape[1] != rank:
+        raise ValueError(f"vectors should be [n, {rank}], not {q.shape}")
+    n_q = int(q.shape[0])
+    ptr_, eids = exclusion_csr(exclude, n_q)
+    ids = np.empty((n_q, max(int(k), 0)), dtype=np.int32)
+    sc = np.empty((n_q, max(int(k), 0)), dtype=np.float32)
+    check(load().als_similar_vectors(ctx, side, int(k), n_q, ptr(q, C.c_float),
+                                     ptr(ptr_, C.c_int64) if ptr_ is not None else None,
+                                     ptr(eids, C.c_int32) if eids is not None and eids.size else None,
+                                     ptr(ids, C.c_int32), ptr(sc, C.c_float)))
+    return ids, sc
+
+
+def similar_timing(ctx):
+    """als_similar_timing: device ms of the last call: [unit image, lists, merge / filter, total]."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.float64)
+    check(load().als_similar_timing(ctx, ptr(out, C.c_double)))
+    return out
+
+
+def similar_stats(ctx):
+    """als_similar_stats of the last call: [rows asked and known, rows without a direction, tier, exact-scan rows]."""
+    import numpy as np
+
+    out = np.zeros(4, dtype=np.int64)
+    check(load().als_similar_stats(ctx, ptr(out, C.c_int64)))
     return out

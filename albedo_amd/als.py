@@ -736,6 +736,54 @@ class ALSModel(_Params):
         """Device ms of the last recommend_vectors_np: exclusions (map + sort), scan, merge, total."""
         return dict(zip(("exclusions", "scan", "merge", "total"), _lib.recommend_vectors_timing(self._h).tolist()))
 
+    # ---- cosine top-k within one side -----------------------------------------------------------
+    def similar_np(self, num, subset=None, side="item"):
+        """(src ids [n], ids [n, num], scores [n, num]): for each requested row of `side` (raw ids in `subset`,
+        caller order, repeats kept; None: every row, ascending) the num <= 64 other rows of the same side with
+        the largest cosine, sorted (score desc, id asc) with -1 / NaN padding (als_similar).  The row itself
+        and rows without a direction (zero, non-finite) are never listed; unknown ids give an all-padding row."""
+        t = self._side(side)
+        if subset is not None:
+            subset = _checked_cast(subset, self._p["userCol"] if t == _lib.ALS_USER else self._p["itemCol"])
+        return _lib.similar(self._h, t, num, subset)
+
+    def _similar_frame(self, side, dataset, num):
+        import pandas as pd
+        col = self._cols(side)[0]
+        sub = None if dataset is None else np.unique(_checked_cast(_column(dataset, col), col))
+        src, ids, sc = self.similar_np(num, sub, side)
+        sims = []
+        for r in range(len(src)):
+            m = ~np.isnan(sc[r])  # padding is told by the NaN score: -1 is a valid raw id
+            sims.append([(int(i), float(s)) for i, s in zip(ids[r][m], sc[r][m])])
+        keep = [i for i in range(len(src)) if sims[i]]
+        return pd.DataFrame({col: src[keep], "similarities": [sims[i] for i in keep]})
+
+    def similarItems(self, dataset, numItems):
+        """For each distinct item of `dataset`'s itemCol (None: every item of the model) the numItems most similar
+        other items by cosine, as a frame (itemCol, similarities) shaped like recommendForItemSubset's; items
+        the model does not know, and items with an empty list, have no row."""
+        return self._similar_frame(_lib.ALS_ITEM, dataset, numItems)
+
+    def similarUsers(self, dataset, numUsers):
+        """similarItems on the user side: frame (userCol, similarities)."""
+        return self._similar_frame(_lib.ALS_USER, dataset, numUsers)
+
+    def similar_vectors_np(self, vectors, num, exclude=None, side="item"):
+        """recommend_vectors_np with the cosine as the score: each row of `vectors` [n, rank] (a folded-in user, an
+        average of repos) against the rows of `side` (als_similar_vectors).  A zero or non-finite vector gives
+        an all-padding list; `exclude` as in recommend_vectors_np."""
+        return _lib.similar_vectors(self._h, self._side(side), vectors, num, self.rank, exclude)
+
+    def similar_timing(self):
+        """Device ms of the last similar_np / similar_vectors_np: unit image, lists, merge / filter, total."""
+        return dict(zip(("unit_image", "lists", "merge", "total"), _lib.similar_timing(self._h).tolist()))
+
+    def similar_stats(self):
+        """Counters of the last similar_np / similar_vectors_np: rows asked and known, rows of the side without a
+        direction, tier (0 scan, 1 passes), rows the passes tier sent to its exact scan."""
+        return dict(zip(("rows", "no_direction", "tier", "rows_exact"), _lib.similar_stats(self._h).tolist()))
+
     def recommendForNewUsers(self, dataset, numItems, excludeKnown=False, explain=None, **fold_kw):
         """recommendForUserSubset for users the model has not seen: their factors are folded in from
         `dataset` (foldIn's keywords apply), then scored against the model's items on the model's own

@@ -384,6 +384,20 @@ static int ctx_common(const als_params* p, als_ctx** out) {
   return ALS_OK;
 }
 
+}  // extern "C"
+
+int albedo::bare_context(int32_t rank, int32_t device, als_ctx** out) {
+  *out = nullptr;
+  als_params p;
+  als_params_default(&p);
+  p.rank = rank;
+  p.device = device;
+  TRYC(validate(&p));
+  return ctx_common(&p, out);
+}
+
+extern "C" {
+
 int als_create(const als_params* p, als_ctx** out) {
   if (!p || !out) return fail(ALS_E_INVALID_ARGUMENT, "null argument");
   *out = nullptr;

@@ -2,7 +2,8 @@
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
 // held-out pair ranking; audit_host.cpp: the row audit; objective_host.cpp: the training loss, both
 // over row_plan.h; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation;
-// query_topk_host.cpp: top-k of caller-supplied vectors): error reporting, the device buffer, the
+// query_topk_host.cpp: top-k of caller-supplied vectors; similar_host.cpp: cosine top-k within one side):
+// error reporting, the device buffer, the
 // stream guards, the row buckets, the per-side state, the context and the few functions one file calls
 // in another.  Not part of the public C ABI (include/albedo_als.h).
 #pragma once
@@ -263,6 +264,11 @@ struct als_ctx {
   // scan, total
   int64_t unseen_stats[4] = {0, 0, 0, 0};
   double unseen_ms[5] = {0, 0, 0, 0, 0};
+  // the last als_similar / als_similar_vectors call: device ms of the unit image, the lists (scan or passes),
+  // merge / filter, total; rows asked and known, rows of the side without a direction, tier (0 scan,
+  // 1 passes), rows the passes tier sent to its exact scan
+  double similar_ms[4] = {0, 0, 0, 0};
+  int64_t similar_stats[4] = {0, 0, 0, 0};
   hipEvent_t evt[5] = {};
   // src ids the last als_recommend / als_evaluate_ndcg sent to the exact rescan, built on demand
   // (als_topk_last_rescan) from the device flags of that call: position p of the call's rows was
@@ -299,6 +305,9 @@ namespace albedo {
 constexpr int EVC_GATHERED = 8;
 
 int set_device(als_ctx* c);
+// A context of rank `rank` on `device` with its streams and events and nothing else: what als_model_create
+// fills from host arrays and als_similar's passes tier from device buffers.  Freed with als_destroy
+int bare_context(int32_t rank, int32_t device, als_ctx** out);
 // both streams idle: before anything rewrites factor buffers with engine-stream copies, or returns to
 // the caller as "done" (world > 1: the last half's gathers run on st2 behind the solve)
 int drain(als_ctx* c);

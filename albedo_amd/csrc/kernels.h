@@ -1,6 +1,6 @@
 // Internal launch interface between the host code (als_engine.cpp, sweep_host.cpp, topk_host.cpp,
 // eval_host.cpp, audit_host.cpp and objective_host.cpp with row_plan.h, foldin_host.cpp, explain_host.cpp,
-// query_topk_host.cpp) and the HIP kernels.  Not part of the public C ABI (include/albedo_als.h).
+// query_topk_host.cpp, similar_host.cpp) and the HIP kernels.  Not part of the public C ABI (include/albedo_als.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -515,5 +515,19 @@ hipError_t synth_fill(uint64_t seed, int rounds, int64_t n_users, int64_t n_item
                       const int64_t* d_deg_prefix, const double* d_cw, const int32_t* d_perm,
                       int32_t* d_user, int32_t* d_item, float* d_rating, int64_t n_slots,
                       int64_t* n_out, hipStream_t s);
+
+// ---- similarity within one side (similar.hip): the unit image behind als_similar / als_similar_vectors ----
+// out [n][ld_out]: row i of `in` ([n][ld_in], `rank` columns used) divided by the square root of its F2J
+// sdot with itself, columns past `rank` zero; a row without a direction (!(s > 0 && s < inf)) is NaN and
+// flag[i] = 0 (flag may be null).  in and out must not overlap
+hipError_t launch_similar_unit(const float* in, int64_t ld_in, int64_t n, int rank, float* out, int64_t ld_out,
+                               int32_t* flag, hipStream_t s);
+// q [n_q][rank]: the unit rows `rows[i]` (null: row i), NaN for a negative row or one without a direction;
+// excl_ptr [n_q + 1] and excl_key [n_q]: each query's own row as its one exclusion, sorted as
+// launch_query_scan reads them
+hipError_t launch_similar_gather(const float* unit, int KP, int rank, const int32_t* flag, const int32_t* rows, int64_t n_q,
+                                 float* q, int64_t* excl_ptr, uint64_t* excl_key, hipStream_t s);
+// out [n][KP]: rows `rows[j]` of the image, in that order
+hipError_t launch_similar_compact(const float* unit, int KP, const int32_t* rows, int64_t n, float* out, hipStream_t s);
 
 }  // namespace albedo

@@ -381,7 +381,7 @@ int als_explain_timing(const als_ctx* ctx, double* out4);
  *                 score NaN (the NaN tells the padding: -1 is a valid raw id).
  * Two calls give identical bits; no floating-point atomics are used.
  * Limits: 1 <= k <= 64, world = 1, n_q < 2^31: ALS_E_UNSUPPORTED beyond them (als_recommend serves larger k
- * for rows the model holds).  Cosine similarity is not offered: normalise the vectors and the factors first.
+ * for rows the model holds).  Cosine similarity: als_similar / als_similar_vectors below.
  * Errors: ALS_E_INVALID_ARGUMENT for a bad side, k < 1, a negative n_q, null q or outputs with n_q > 0, an
  * excl_ptr that is negative or does not ascend, a null excl_ids with a non-empty range, more than 2^31 - 1
  * exclusions; ALS_E_STATE when dst_side has no factors.  n_q = 0 is ALS_OK.
@@ -397,6 +397,65 @@ int als_recommend_vectors(als_ctx* ctx, int dst_side, int32_t k,
 /* Device time of the last als_recommend_vectors call from HIP events on the context's stream (ms):
  * out[0] = exclusion map + sort (0 without exclusions), out[1] = scan, out[2] = merge, out[3] = total. */
 int als_recommend_vectors_timing(const als_ctx* ctx, double* out4);
+
+/* Cosine top-k within one side: for each requested row of `side` (every row, ascending id, when subset ==
+ * NULL) the best k OTHER rows of the same side ("repos like this one", "users like this user").
+ *   Unit image    every row y of the side as als_get_factors returns it (fp32, `rank` columns) gives
+ *                 s = F2J sdot(y, y) (fp32, left to right from +0.0, multiply and add rounded separately),
+ *                 r = sqrt(s) and u_c = y_c / r, square root and divide correctly rounded in fp32: numpy's
+ *                 float32 sqrt and /.  A row has no direction when !(s > 0 && s < inf): all zero, NaN or
+ *                 +-inf inside, s overflowed or underflowed to 0.  Its unit row is NaN.
+ *   Score         cos(i, j) = F2J sdot(u_i, u_j): als_recommend_vectors' scoring on the unit image.  Scaling a
+ *                 row by a power of two (no overflow, no underflow) leaves its unit row, and so every score,
+ *                 bit-identical; a row against a copy of itself scores sdot(u, u), which need not be 1.0f.
+ *                 To first order the score is within (rank + 4) * 2^-24 of the fp64 cosine.
+ *   Listed rows   the row itself is never listed; rows without a direction are never listed and their own
+ *                 list is all padding; an id of `subset` the side does not know gives an all-padding row, a
+ *                 repeated id one row each, in the caller's order.
+ *   Selection     (score desc, id asc), -0.0 and +0.0 tie, a NaN score is never listed; lists are dense,
+ *                 padded with id -1 / score NaN: als_recommend's order and padding.
+ *   Output        src_ids_out [n] (may be NULL) echoes the requested ids; ids_out / scores_out [n][k] with
+ *                 n = n_subset, or the side's row count when subset == NULL.
+ * Two tiers give the same bits: the query scan of als_recommend_vectors for few rows, and for many rows the
+ * passes of als_recommend_unseen on a transient model whose two sides are both the unit image (rows without
+ * a direction left out), built on the device and destroyed with the call.  The tier follows the row count;
+ * ALBEDO_SIMILAR_TIER=scan|passes in the environment (read per call) forces one.  The default goes to the passes
+ * from 2^18 rows asked; what that rests on, and where it is not backed by a measurement, is in DESIGN.md
+ * ("Similar rows within one side").  ALBEDO_SIMILAR_TRACE=1 (diagnostic) makes the passes tier print one line
+ * on stderr with the transient model's build time, timers and counters.  The unit image is rebuilt by every
+ * call; nothing is cached on the context.
+ * Limits: 1 <= k <= 64, world = 1, n_subset < 2^31: ALS_E_UNSUPPORTED beyond them.
+ * Errors: ALS_E_INVALID_ARGUMENT for a bad side, k < 1, a negative n_subset, null ids_out or scores_out;
+ * ALS_E_STATE when `side` has no factors.  n_subset = 0 is ALS_OK.  Only the one side is needed: a model
+ * created with zero users serves als_similar(ALS_ITEM).
+ * The model is read-only: factors, bases, Gram caches, sweep timings, path stats and the counters and timings
+ * of als_recommend, als_recommend_unseen, als_recommend_vectors, als_fold_in and als_explain are unchanged,
+ * and a call between two half-sweeps leaves the fit bit-identical.  Two calls give identical bits; no
+ * floating-point atomics are used.  Fitted contexts, forks and contexts from als_model_create may call it. */
+int als_similar(als_ctx* ctx, int side, int32_t k,
+                const int32_t* subset /* raw ids or NULL */, int64_t n_subset,
+                int32_t* src_ids_out /* [n] or NULL */, int32_t* ids_out /* [n][k] */, float* scores_out /* [n][k] */);
+/* The same for caller-supplied vectors (a folded-in user, an average of repos): q[i] ([n_q][rank]) goes
+ * through the unit rule above (a q[i] without a direction: all padding), then exactly als_recommend_vectors'
+ * contract on the unit image of dst_side, exclusion lists included (a query that is a row of dst_side lists
+ * that row unless its id is excluded).  Always the scan tier.
+ * Limits: 1 <= k <= 64, world = 1, n_q < 2^31, fewer than 2^31 exclusions: ALS_E_UNSUPPORTED beyond them.
+ * Errors: ALS_E_INVALID_ARGUMENT for a bad side, k < 1, a negative n_q, null q or outputs with n_q > 0, an
+ * excl_ptr that is negative or does not ascend, a null excl_ids with a non-empty range; ALS_E_STATE when
+ * dst_side has no factors.  n_q = 0 is ALS_OK.  Read-only like als_similar. */
+int als_similar_vectors(als_ctx* ctx, int dst_side, int32_t k,
+                        int64_t n_q, const float* q /* [n_q][rank] */,
+                        const int64_t* excl_ptr /* [n_q+1] or NULL */, const int32_t* excl_ids /* raw dst ids */,
+                        int32_t* ids_out /* [n_q][k] */, float* scores_out /* [n_q][k] */);
+/* Device time of the last als_similar / als_similar_vectors call (ms, HIP events): out[0] = unit image (with
+ * the queries and their exclusion keys in the scan tier, the compaction in the passes tier), out[1] = the lists
+ * (the scan, or the passes' plan, lists and exact scan), out[2] = merge (scan tier) or filter (passes tier),
+ * out[3] = total. */
+int als_similar_timing(const als_ctx* ctx, double* out4);
+/* Counters of the last call: out[0] = rows asked that the side knows (als_similar_vectors: n_q), out[1] = rows
+ * of the side without a direction, out[2] = tier used (0 scan, 1 passes), out[3] = rows the passes tier sent
+ * to its exact scan. */
+int als_similar_stats(const als_ctx* ctx, int64_t* out4);
 
 /* ---- observability ---------------------------------------------------------------------------- */
 /* Per-stage device time (ms) of the last half-sweeps: see ALS_T_* indices. n = array length. */
