@@ -1,8 +1,9 @@
 // What the host translation units share (als_engine.cpp: contexts, ingest, init, the C ABI;
 // sweep_host.cpp: the row layout and the half-sweep; topk_host.cpp: top-k and NDCG; eval_host.cpp:
 // held-out pair ranking; audit_host.cpp: the row audit; objective_host.cpp: the training loss, both
-// over row_plan.h; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation;
-// query_topk_host.cpp: top-k of caller-supplied vectors; similar_host.cpp: cosine top-k within one side):
+// over row_plan.h; foldin_host.cpp: the fold-in; explain_host.cpp: the explanation, both over fold_host.h;
+// query_topk_host.cpp: top-k of caller-supplied vectors, with the exclusion lists and the scan tier that
+// similar_host.cpp (cosine top-k within one side) runs too):
 // error reporting, the device buffer, the
 // stream guards, the row buckets, the per-side state, the context and the few functions one file calls
 // in another.  Not part of the public C ABI (include/albedo_als.h).
@@ -113,6 +114,13 @@ struct Drain {
   }
 };
 
+// one stage mark: an event created in the empty slot *e and recorded on s
+inline hipError_t mark_event(hipEvent_t* e, hipStream_t s) {
+  hipError_t r = hipEventCreate(e);
+  if (r != hipSuccess) return r;
+  return hipEventRecord(*e, s);
+}
+
 template <int N>
 struct Marks {  // stage marks on the stream
   hipEvent_t e[N] = {};
@@ -123,11 +131,7 @@ struct Marks {  // stage marks on the stream
     for (hipEvent_t x : e)
       if (x) (void)hipEventDestroy(x);
   }
-  hipError_t mark(int i, hipStream_t s) {
-    hipError_t r = hipEventCreate(&e[i]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[i], s);
-  }
+  hipError_t mark(int i, hipStream_t s) { return mark_event(&e[i], s); }
 };
 
 // Row buckets, one table row each, in list order: the order of Side::d_rows, which fixes the launch
@@ -330,6 +334,38 @@ int allgather_host(als_ctx* c, float* buf, int64_t n);
 int objective_ready(const als_ctx* c, const char* who);
 // als_objective behind its argument checks: dst side t, both sides hold factors, the device is set
 int objective(als_ctx* c, int t, double* row_loss_out, als_objective_t* out);
+
+// ---- query_topk_host.cpp -------------------------------------------------------------------------
+// The exclusion lists of als_recommend_vectors and als_similar_vectors (`who`, named in the messages): checks
+// excl_ptr [n_q + 1] and *excl_ids; *ptr0 becomes the ranges shifted to start at 0, empty when the call has
+// none, and *excl_ids moves to the first range.  More than 2^31 - 1 exclusions return `too_many`, the one
+// code the two calls do not share
+int exclusion_ranges(const char* who, int too_many, int64_t n_q, const int64_t* excl_ptr, const int32_t** excl_ids,
+                     std::vector<int64_t>* ptr0);
+// Those lists on the device, declared before the caller's Drain.  upload queues the copies on c->st (nothing
+// when ptr0 is empty); map leaves each query's range of `keys` ascending (query_map_exclusions) against the
+// id table d_ids [n_dst]
+struct Exclusions {
+  DevBuf d_ptr, d_eid, d_key, d_keys, d_tmp;
+  int64_t n_e = 0;
+  size_t temp_bytes = 0;
+  int upload(als_ctx* c, int64_t n_q, const std::vector<int64_t>& ptr0, const int32_t* excl_ids);
+  int map(als_ctx* c, int64_t n_q, const int32_t* d_ids, int64_t n_dst);
+  const int64_t* ptr() const { return n_e > 0 ? d_ptr.as<int64_t>() : nullptr; }  // null: no exclusions
+  const uint64_t* keys() const { return n_e > 0 ? d_keys.as<uint64_t>() : nullptr; }
+};
+// The slice partials and the lists of the scan tier, declared before the caller's Drain.  The caller chooses
+// where ensure's four allocations fall among its stage marks
+struct ScanBuffers {
+  DevBuf d_ps, d_pr, d_oi, d_os;
+  int ensure(const als_ctx* c, int64_t n_dst, int64_t n_q, int k);
+};
+// The scan tier on device inputs: the k best rows of d_Y [n_dst][KP] for each query of d_q [n_q][rank], less
+// its exclusions, as raw ids in ids_out / scores_out on the host; the stream is synchronised on return.  The
+// events of scan done and merge done go into the two empty slots: the caller's timing is its own
+int scan_lists(als_ctx* c, const ScanBuffers& b, int k, const float* d_Y, int64_t n_dst, const float* d_q, int64_t n_q,
+               const int64_t* d_ptr, const uint64_t* d_keys, const int32_t* d_ids, hipEvent_t* scan_done,
+               hipEvent_t* merge_done, int32_t* ids_out, float* scores_out);
 
 // ---- sweep_host.cpp ------------------------------------------------------------------------------
 // Everything that depends on the rank / light-row limit rather than on the ratings: degree buckets,

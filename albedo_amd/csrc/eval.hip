@@ -16,34 +16,22 @@
 //            to the host evaluator's.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cstdint>
 #include "device_common.h"
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
 namespace {
-
-inline int ev_grid(int64_t n, int per) {
-  const int64_t b = (n + per - 1) / per;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(b, 16384));
-}
 
 // raw user id -> dense row (binary search over the ascending ids); unknown ids -> 0xFFFFFFFF, which
 // sorts last and is dropped (the evaluator's inner join)
 __global__ void ev_map_rows_kernel(const int32_t* __restrict__ user, int64_t n, const int32_t* __restrict__ ids,
                                    int64_t n_ids, uint32_t* __restrict__ row, uint32_t* __restrict__ idx) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t u = user[i];
-    int64_t lo = 0, hi = n_ids;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (ids[mid] < u) lo = mid + 1;
-      else hi = mid;
-    }
-    row[i] = (lo < n_ids && ids[lo] == u) ? (uint32_t)lo : 0xFFFFFFFFu;
+    const int64_t r = find_id(ids, n_ids, user[i]);
+    row[i] = r >= 0 ? (uint32_t)r : 0xFFFFFFFFu;
     idx[i] = (uint32_t)i;
   }
 }
@@ -148,34 +136,23 @@ __global__ __launch_bounds__(256) void ev_ndcg_kernel(const int32_t* __restrict_
 }  // namespace
 
 size_t eval_sort_temp_bytes(int64_t n) {
-  size_t a = 0, b = 0, c = 0;
+  size_t a = 0;
   (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                   (uint32_t*)nullptr, (size_t)n, 0, 32, (hipStream_t)0);
-  (void)rocprim::run_length_encode(nullptr, b, (uint32_t*)nullptr, (size_t)n, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                   (int64_t*)nullptr, (hipStream_t)0);
-  (void)rocprim::exclusive_scan(nullptr, c, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n,
-                                rocprim::plus<int64_t>(), (hipStream_t)0);
-  return std::max(a, std::max(b, c));
+  return std::max(a, group_temp_bytes<false, false>(n));
 }
 
 hipError_t eval_group_users(const int32_t* user, int64_t n, const int32_t* ids, int64_t n_ids, void* temp,
                             size_t temp_bytes, uint32_t* row, uint32_t* row_sorted, uint32_t* idx, uint32_t* idx_sorted,
                             uint32_t* runs, int32_t* counts, int64_t* offsets, int64_t* n_runs, hipStream_t s) {
-  ev_map_rows_kernel<<<ev_grid(n, 256), 256, 0, s>>>(user, n, ids, n_ids, row, idx);
+  ev_map_rows_kernel<<<front_grid(n), 256, 0, s>>>(user, n, ids, n_ids, row, idx);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   size_t tb = temp_bytes;
   e = rocprim::radix_sort_pairs(temp, tb, row, row_sorted, idx, idx_sorted, (size_t)n, 0, 32, s);
   if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  e = rocprim::run_length_encode(temp, tb, row_sorted, (size_t)n, runs, counts, n_runs, s);
-  if (e != hipSuccess) return e;
-  int64_t nr = 0;
-  e = hipMemcpyAsync(&nr, n_runs, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  return rocprim::exclusive_scan(temp, tb, counts, offsets, (int64_t)0, (size_t)nr, rocprim::plus<int64_t>(), s);
+  int64_t nr = 0;  // the host caller reads *n_runs itself
+  return group_runs<false>(temp, temp_bytes, row_sorted, n, runs, counts, offsets, n_runs, &nr, s);
 }
 
 hipError_t eval_actual_lists(const uint32_t* idx_sorted, const int64_t* offsets, const int32_t* counts, int64_t n_runs,

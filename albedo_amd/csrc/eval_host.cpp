@@ -18,27 +18,11 @@
 namespace albedo {
 namespace {
 
-// Stage marks on the stream: ms[i] = device time between mark i and mark i + 1
-struct StageClock {
-  hipEvent_t e[6] = {};
-  int n = 0;
-  StageClock() = default;
-  StageClock(const StageClock&) = delete;
-  StageClock& operator=(const StageClock&) = delete;
-  ~StageClock() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t mark(hipStream_t s) {
-    if (n >= 6) return hipErrorInvalidValue;
-    hipError_t r = hipEventCreate(&e[n]);
-    if (r != hipSuccess) return r;
-    return hipEventRecord(e[n++], s);
-  }
-  void read(double* ms5) const {  // after the stream is synchronised
-    for (int i = 0; i < 5; ++i) ms5[i] = i + 1 < n ? event_ms(e[i], e[i + 1]) : 0.0;
-  }
-};
+// Stage marks 0 .. n - 1 were taken in order (at most six a call); after the stream is synchronised
+// ms5[i] = device time between mark i and mark i + 1, 0 for the stages the call did not reach
+void stage_ms(const Marks<6>& clk, int n, double* ms5) {
+  for (int i = 0; i < 5; ++i) ms5[i] = i + 1 < n ? event_ms(clk.e[i], clk.e[i + 1]) : 0.0;
+}
 
 // The lists of one call on the device: run r (user row rows[r], ascending) has len[r] entries in
 // items / scores [n_runs][width]; len[r] = 0 when every score of the user was NaN
@@ -61,9 +45,9 @@ int check_pair_args(const als_ctx* c, int32_t top_k, int32_t width, const char* 
   return ALS_OK;
 }
 
-// map, group, score, select of n > 0 pairs on c->st (marks 0 .. 4 of the clock)
+// map, group, score, select of n > 0 pairs on c->st (marks 0 .. 4 of the clock, counted in n_marks)
 int build_pair_lists(als_ctx* c, int top_k, int width, int64_t n, const int32_t* user, const int32_t* item,
-                     PairLists& L, StageClock& clk) {
+                     PairLists& L, Marks<6>& clk, int& n_marks) {
   Side& S = c->s[ALS_USER];
   Side& T = c->s[ALS_ITEM];
   hipStream_t st = c->st;
@@ -81,15 +65,15 @@ int build_pair_lists(als_ctx* c, int top_k, int width, int64_t n, const int32_t*
   HIPCHK(hipMemcpyAsync(L.d_item.p, item, n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(L.d_uids.p, S.ids.data(), S.n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(L.d_iids.p, T.ids.data(), T.n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   HIPCHK(pairs_map(L.d_user.as<int32_t>(), L.d_item.as<int32_t>(), n, L.d_uids.as<int32_t>(), S.n,
                    L.d_iids.as<int32_t>(), T.n, L.d_urow.as<uint32_t>(), L.d_irow.as<uint32_t>(), st));
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   int64_t nr = 0;
   HIPCHK(pairs_group(n, S.n, L.d_tmp.p, tb, L.d_urow.as<uint32_t>(), L.d_urows.as<uint32_t>(), L.d_irow.as<uint32_t>(),
                      L.d_irows.as<uint32_t>(), L.d_runs.as<uint32_t>(), L.d_cnt.as<int32_t>(), L.d_off.as<int64_t>(),
                      L.d_nr.as<int64_t>(), &nr, st));
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   if (nr <= 0 || nr > n) return fail(ALS_E_STATE, "pair ranking: run count out of range");
   L.rows.resize(nr);
   std::vector<int32_t> cnt(nr);
@@ -105,12 +89,12 @@ int build_pair_lists(als_ctx* c, int top_k, int width, int64_t n, const int32_t*
   L.n_runs = nr;
   L.len.assign(nr, 0);
   if (nr == 0) {
-    for (int i = 0; i < 2; ++i) HIPCHK(clk.mark(st));
+    for (int i = 0; i < 2; ++i) HIPCHK(clk.mark(n_marks++, st));
     return ALS_OK;
   }
   HIPCHK(pairs_score(c->KP, c->p.rank, S.d_orig.as<float>(), T.d_orig.as<float>(), L.d_urows.as<uint32_t>(),
                      L.d_irows.as<uint32_t>(), L.d_iids.as<int32_t>(), n_live, L.d_ent.as<uint2>(), st));
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   HIPCHK(L.d_items.ensure(nr * width * 4));
   HIPCHK(L.d_scores.ensure(nr * width * 4));
   HIPCHK(L.d_len.ensure(nr * 4));
@@ -151,7 +135,7 @@ int build_pair_lists(als_ctx* c, int top_k, int width, int64_t n, const int32_t*
                              L.d_scores.as<float>(), L.d_len.as<int32_t>(), st));
     HIPCHK(hipStreamSynchronize(st));  // the host arrays above are read by the copies until here
   }
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   HIPCHK(hipMemcpyAsync(L.len.data(), L.d_len.p, nr * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return ALS_OK;
@@ -184,10 +168,11 @@ int als_rank_pairs(als_ctx* c, int32_t top_k, int32_t width, int64_t n, const in
   const Side& S = c->s[ALS_USER];
   if (n <= 0 || S.n == 0 || c->s[ALS_ITEM].n == 0) return ALS_OK;
   PairLists L;
-  StageClock clk;
+  Marks<6> clk;
+  int n_marks = 0;
   Drain queued{c->st};
-  TRYC(build_pair_lists(c, top_k, width, n, user, item, L, clk));
-  clk.read(c->eval_ms);
+  TRYC(build_pair_lists(c, top_k, width, n, user, item, L, clk, n_marks));
+  stage_ms(clk, n_marks, c->eval_ms);
   int64_t nu = 0;
   for (int64_t r = 0; r < L.n_runs; ++r) nu += L.len[r] > 0;
   *n_users_out = nu;
@@ -232,9 +217,10 @@ int als_evaluate_pairs(als_ctx* c, int32_t metric, int32_t top_k, int32_t k, int
   PairLists L;
   DevBuf d_au, d_ai, d_ak, d_row, d_rows, d_idx, d_idxs, d_runs, d_cnt, d_off, d_nr, d_tmp, d_act, d_actn, d_gain;
   DevBuf d_prow, d_arow, d_vals;
-  StageClock clk;
+  Marks<6> clk;
+  int n_marks = 0;
   Drain queued{st};
-  TRYC(build_pair_lists(c, top_k, k, n_pairs, user, item, L, clk));
+  TRYC(build_pair_lists(c, top_k, k, n_pairs, user, item, L, clk, n_marks));
   // intoUserActualItems of the actual rows, restricted to the model's users (as als_evaluate_ndcg)
   HIPCHK(d_au.ensure(n_act * 4));
   HIPCHK(d_ai.ensure(n_act * 4));
@@ -272,7 +258,7 @@ int als_evaluate_pairs(als_ctx* c, int32_t metric, int32_t top_k, int32_t k, int
   *n_users_out = ne;
   if (ne == 0) {
     HIPCHK(hipStreamSynchronize(st));
-    clk.read(c->eval_ms);
+    stage_ms(clk, n_marks, c->eval_ms);
     return ALS_OK;
   }
   HIPCHK(d_act.ensure(na * k * 4));
@@ -292,11 +278,11 @@ int als_evaluate_pairs(als_ctx* c, int32_t metric, int32_t top_k, int32_t k, int
   HIPCHK(eval_metric(metric, L.d_items.as<int32_t>(), k, L.d_len.as<int32_t>(), 0, d_prow.as<int32_t>(),
                      d_act.as<int32_t>(), d_actn.as<int32_t>(), d_arow.as<int32_t>(), ne, k, d_gain.as<double>(),
                      d_vals.as<double>(), st));
-  HIPCHK(clk.mark(st));
+  HIPCHK(clk.mark(n_marks++, st));
   std::vector<double> vals(ne);
   HIPCHK(hipMemcpyAsync(vals.data(), d_vals.p, ne * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  clk.read(c->eval_ms);
+  stage_ms(clk, n_marks, c->eval_ms);
   double sum = 0.0;  // mean over users in ascending id order (RankingMetrics: RDD mean)
   for (int64_t i = 0; i < ne; ++i) sum += vals[i];
   *mean_out = sum / (double)ne;

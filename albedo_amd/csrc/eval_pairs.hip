@@ -25,37 +25,21 @@
 // still folds the two zeros together, and a score is recovered from its key.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cstdint>
 #include "device_common.h"
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
 namespace {
 
-inline int ep_grid(int64_t n, int per) {
-  const int64_t b = (n + per - 1) / per;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(b, 16384));
-}
-
-__device__ __forceinline__ int64_t ep_find(const int32_t* __restrict__ ids, int64_t n_ids, int32_t v) {
-  int64_t lo = 0, hi = n_ids;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < n_ids && ids[lo] == v) ? lo : -1;
-}
-
 __global__ void ep_map_kernel(const int32_t* __restrict__ user, const int32_t* __restrict__ item, int64_t n,
                               const int32_t* __restrict__ uids, int64_t n_u, const int32_t* __restrict__ iids,
                               int64_t n_i, uint32_t* __restrict__ urow, uint32_t* __restrict__ irow) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t u = ep_find(uids, n_u, user[i]);
-    const int64_t v = ep_find(iids, n_i, item[i]);
+    const int64_t u = find_id(uids, n_u, user[i]);
+    const int64_t v = find_id(iids, n_i, item[i]);
     const bool live = u >= 0 && v >= 0;
     urow[i] = live ? (uint32_t)u : (uint32_t)n_u;  // cold start "drop": behind every user, never scored
     irow[i] = live ? (uint32_t)v : 0u;
@@ -272,21 +256,17 @@ int ep_key_bits(int64_t n_u) {  // bits of the largest sort key, n_u
 }  // namespace
 
 size_t pairs_sort_temp_bytes(int64_t n, int64_t n_users) {
-  size_t a = 0, b = 0, c = 0;
+  size_t a = 0;
   (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                   (uint32_t*)nullptr, (size_t)n, 0, ep_key_bits(n_users), (hipStream_t)0);
-  (void)rocprim::run_length_encode(nullptr, b, (uint32_t*)nullptr, (size_t)n, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                   (int64_t*)nullptr, (hipStream_t)0);
-  (void)rocprim::exclusive_scan(nullptr, c, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n,
-                                rocprim::plus<int64_t>(), (hipStream_t)0);
-  return std::max(a, std::max(b, c));
+  return std::max(a, group_temp_bytes<false, false>(n));
 }
 
 hipError_t pairs_map(const int32_t* user, const int32_t* item, int64_t n, const int32_t* uids, int64_t n_u,
                      const int32_t* iids, int64_t n_i, uint32_t* urow, uint32_t* irow, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   if (n_u >= (int64_t)0xFFFFFFFF) return hipErrorInvalidValue;
-  ep_map_kernel<<<ep_grid(n, 256), 256, 0, s>>>(user, item, n, uids, n_u, iids, n_i, urow, irow);
+  ep_map_kernel<<<front_grid(n), 256, 0, s>>>(user, item, n, uids, n_u, iids, n_i, urow, irow);
   return hipGetLastError();
 }
 
@@ -297,21 +277,13 @@ hipError_t pairs_group(int64_t n, int64_t n_u, void* temp, size_t temp_bytes, co
   hipError_t e = rocprim::radix_sort_pairs(temp, tb, urow, urow_sorted, irow, irow_sorted, (size_t)n, 0,
                                            ep_key_bits(n_u), s);
   if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  e = rocprim::run_length_encode(temp, tb, urow_sorted, (size_t)n, runs, counts, n_runs, s);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(n_runs_host, n_runs, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  return rocprim::exclusive_scan(temp, tb, counts, offsets, (int64_t)0, (size_t)*n_runs_host, rocprim::plus<int64_t>(),
-                                 s);
+  return group_runs<false>(temp, temp_bytes, urow_sorted, n, runs, counts, offsets, n_runs, n_runs_host, s);
 }
 
 hipError_t pairs_score(int KP, int kreal, const float* U, const float* V, const uint32_t* urow_sorted,
                        const uint32_t* irow_sorted, const int32_t* iids, int64_t n_live, uint2* ent, hipStream_t s) {
   if (n_live <= 0) return hipSuccess;
-  const int grid = ep_grid((n_live + 63) / 64, 2);
+  const int grid = front_grid((n_live + 63) / 64, 2);
   switch (KP) {
     case 64: ep_score_kernel<64><<<grid, 128, 0, s>>>(U, V, urow_sorted, irow_sorted, iids, n_live, kreal, ent); break;
     case 128: ep_score_kernel<128><<<grid, 128, 0, s>>>(U, V, urow_sorted, irow_sorted, iids, n_live, kreal, ent); break;

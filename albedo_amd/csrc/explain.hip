@@ -28,31 +28,18 @@
 //   Nothing per (rating, pair) reaches global memory; the outputs are written once per pair, at its input slot.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "fold_front.h"
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
 
 namespace {
-
-inline int explain_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
-
-__device__ __forceinline__ int64_t explain_lower_bound(const int32_t* __restrict__ ids, int64_t n, int32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __global__ void explain_pair_kernel(const int32_t* __restrict__ pair_row, const int32_t* __restrict__ pair_target,
                                     int64_t n_pairs, const int32_t* __restrict__ row_ids, int64_t n_rows,
@@ -60,18 +47,10 @@ __global__ void explain_pair_kernel(const int32_t* __restrict__ pair_row, const 
                                     uint32_t* __restrict__ target) {
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_pairs; p += (int64_t)gridDim.x * blockDim.x) {
     const int32_t rv = pair_row[p], tv = pair_target[p];
-    const int64_t r = explain_lower_bound(row_ids, n_rows, rv), t = explain_lower_bound(src_ids, n_src, tv);
+    const int64_t r = lower_bound_id(row_ids, n_rows, rv), t = lower_bound_id(src_ids, n_src, tv);
     const bool ok = r < n_rows && row_ids[r] == rv && t < n_src && src_ids[t] == tv;
     target[p] = ok ? (uint32_t)t : EXPLAIN_NONE;
     key[p] = ((uint64_t)(ok ? (uint32_t)r : EXPLAIN_NONE) << 32) | (uint32_t)p;
-  }
-}
-
-__global__ void explain_split_kernel(const uint64_t* __restrict__ key, int64_t n, uint32_t* __restrict__ hi,
-                                     uint32_t* __restrict__ slot) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    hi[i] = (uint32_t)(key[i] >> 32);
-    slot[i] = (uint32_t)key[i];
   }
 }
 
@@ -308,15 +287,7 @@ hipError_t explain_launch(const ExplainArgs& a, int n_wg, hipStream_t s) {
 }  // namespace
 
 size_t explain_sort_temp_bytes(int64_t n) {
-  size_t a = 0, b = 0, c = 0, d = 0;
-  (void)rocprim::radix_sort_keys(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  (void)rocprim::run_length_encode(nullptr, b, (uint32_t*)nullptr, (size_t)n, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                   (int64_t*)nullptr, (hipStream_t)0);
-  (void)rocprim::exclusive_scan(nullptr, c, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1,
-                                rocprim::plus<int64_t>(), (hipStream_t)0);
-  (void)rocprim::radix_sort_pairs_desc(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                       (int32_t*)nullptr, (size_t)n, 0, 32, (hipStream_t)0);
-  return std::max(std::max(a, b), std::max(c, d));
+  return std::max(sort_keys64_temp_bytes(n), group_temp_bytes<true, true>(n));
 }
 
 hipError_t explain_map_pairs(const int32_t* pair_row_id, const int32_t* pair_target_id, int64_t n_pairs,
@@ -326,38 +297,25 @@ hipError_t explain_map_pairs(const int32_t* pair_row_id, const int32_t* pair_tar
   if (n_pairs <= 0 || n_pairs > (int64_t)0x7FFFFFFF || n_rows <= 0 || n_rows >= (int64_t)EXPLAIN_NONE ||
       n_src >= (int64_t)EXPLAIN_NONE)
     return hipErrorInvalidValue;
-  explain_pair_kernel<<<explain_grid(n_pairs), 256, 0, s>>>(pair_row_id, pair_target_id, n_pairs, row_ids, n_rows,
+  explain_pair_kernel<<<front_grid(n_pairs), 256, 0, s>>>(pair_row_id, pair_target_id, n_pairs, row_ids, n_rows,
                                                             src_ids, n_src, x.key, x.target);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   size_t tb = temp_bytes;
   e = rocprim::radix_sort_keys(temp, tb, x.key, x.key_sorted, (size_t)n_pairs, 0, 64, s);
   if (e != hipSuccess) return e;
-  explain_split_kernel<<<explain_grid(n_pairs), 256, 0, s>>>(x.key_sorted, n_pairs, x.hi, x.slot);
-  e = hipMemsetAsync(x.counts, 0, (size_t)(n_pairs + 1) * 4, s);
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  e = rocprim::run_length_encode(temp, tb, x.hi, (size_t)n_pairs, x.runs, x.counts, x.n_runs, s);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(n_runs_host, x.n_runs, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  split_keys_kernel<<<front_grid(n_pairs), 256, 0, s>>>(x.key_sorted, n_pairs, x.hi, x.slot);
+  e = group_runs<true>(temp, temp_bytes, x.hi, n_pairs, x.runs, x.counts, x.ptr, x.n_runs, n_runs_host, s);
   if (e != hipSuccess) return e;
   const int64_t nu = *n_runs_host;
-  if (nu <= 0 || nu > n_pairs) return hipErrorInvalidValue;
-  tb = temp_bytes;
-  e = rocprim::exclusive_scan(temp, tb, x.counts, x.ptr, (int64_t)0, (size_t)nu + 1, rocprim::plus<int64_t>(), s);
-  if (e != hipSuccess) return e;
-  explain_deg_kernel<<<explain_grid(nu), 256, 0, s>>>(x.runs, nu, row_deg, x.deg, x.iota);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  return rocprim::radix_sort_pairs_desc(temp, tb, x.deg, x.deg_sorted, x.iota, x.order, (size_t)nu, 0, 32, s);
+  explain_deg_kernel<<<front_grid(nu), 256, 0, s>>>(x.runs, nu, row_deg, x.deg, x.iota);
+  return degree_order<false>(temp, temp_bytes, x.deg, x.deg_sorted, x.iota, x.order, nu, s);
 }
 
 hipError_t launch_explain_fill(int64_t n_pairs, int m, double* total, int32_t* ids, double* contrib, hipStream_t s) {
   if (n_pairs <= 0) return hipSuccess;
   if (m < 1 || m > EXPLAIN_MAX_M) return hipErrorInvalidValue;
-  explain_fill_kernel<<<explain_grid(n_pairs * m), 256, 0, s>>>(n_pairs, n_pairs * m, total, ids, contrib);
+  explain_fill_kernel<<<front_grid(n_pairs * m), 256, 0, s>>>(n_pairs, n_pairs * m, total, ids, contrib);
   return hipGetLastError();
 }
 

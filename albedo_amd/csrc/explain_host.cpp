@@ -1,9 +1,9 @@
 // als_explain: host side of the explanation (explain.hip).  The call does what the fold-in does up to the
-// factorisation (foldin_host.cpp): the src side's factors in the original basis, the fp64 src Gram from the
-// side's fold-in cache (or formed there), the triples as a CSR on the device.  It then maps the pairs onto that
-// CSR and runs one workgroup per row that a valid pair names.  It reads the model and writes nothing of it; the
-// fold-in's timing and stats are not touched either.  Every buffer but the cached Gram (Side::d_foldG) is owned
-// by the call.
+// factorisation, through the fold-in's own host code (FoldFront, fold_host.h): the src side's factors in the
+// original basis, the fp64 src Gram from the side's fold-in cache (or formed there), the triples as a CSR on
+// the device.  It maps the pairs onto that CSR and runs one workgroup per row that a valid pair names.  It
+// reads the model and writes nothing of it; the fold-in's timing and stats are not touched either.  Every
+// buffer but the cached Gram (Side::d_foldG) is owned by the call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +15,7 @@
 
 #include "albedo_als.h"
 #include "engine.h"
+#include "fold_host.h"
 #include "kernels.h"
 
 using namespace albedo;
@@ -32,25 +33,13 @@ void fill_unexplained(int64_t n_pairs, int32_t m, double* total, int32_t* ids, d
 int explain(als_ctx* c, int side, double reg, double alpha, int implicit, int64_t n, const int32_t* row_id,
             const int32_t* src_id, const float* rating, int64_t n_pairs, const int32_t* pair_row_id,
             const int32_t* pair_target_id, int32_t m, double* total_out, int32_t* src_ids_out, double* contrib_out) {
-  Side& S = c->s[1 - side];
-  const int KP = c->KP, k = c->p.rank;
   hipStream_t st = c->st;
   TRYC(materialize(c, 1 - side));
-  DevBuf d_row, d_src, d_val, d_sids, d_key, d_keys, d_vals, d_hi, d_col, d_runs, d_cnt, d_ptr, d_nr, d_ids, d_deg, d_degs;
-  DevBuf d_iota, d_order, d_tmp, d_slab, d_scratch, d_bad;
+  FoldFront F;
   DevBuf p_row, p_tgt, p_key, p_keys, p_target, p_hi, p_slot, p_runs, p_cnt, p_ptr, p_nr, p_deg, p_degs, p_iota, p_order;
   DevBuf d_total, d_oids, d_contrib;
   Marks<4> clk;
   Drain queued{st};
-  for (DevBuf* b : {&d_row, &d_src, &d_val, &d_vals, &d_hi, &d_col, &d_runs, &d_ids, &d_deg, &d_degs, &d_iota, &d_order})
-    HIPCHK(b->ensure((size_t)n * 4));
-  HIPCHK(d_cnt.ensure((size_t)(n + 1) * 4));
-  HIPCHK(d_key.ensure((size_t)n * 8));
-  HIPCHK(d_keys.ensure((size_t)n * 8));
-  HIPCHK(d_ptr.ensure((size_t)(n + 1) * 8));
-  HIPCHK(d_nr.ensure(8));
-  HIPCHK(d_bad.ensure(4));
-  HIPCHK(d_sids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));
   for (DevBuf* b : {&p_row, &p_tgt, &p_target, &p_hi, &p_slot, &p_runs, &p_deg, &p_degs, &p_iota, &p_order})
     HIPCHK(b->ensure((size_t)n_pairs * 4));
   HIPCHK(p_cnt.ensure((size_t)(n_pairs + 1) * 4));
@@ -61,35 +50,11 @@ int explain(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   HIPCHK(d_total.ensure((size_t)n_pairs * 8));
   HIPCHK(d_oids.ensure((size_t)n_pairs * m * 4));
   HIPCHK(d_contrib.ensure((size_t)n_pairs * m * 8));
-  const size_t tb = std::max(fold_sort_temp_bytes(n), explain_sort_temp_bytes(n_pairs));
-  HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
-  HIPCHK(hipMemcpyAsync(d_row.p, row_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_src.p, src_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_val.p, rating, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_sids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
+  TRYC(F.upload(c, side, n, row_id, src_id, rating, explain_sort_temp_bytes(n_pairs)));  // one temp buffer for both maps
   HIPCHK(hipMemcpyAsync(p_row.p, pair_row_id, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(p_tgt.p, pair_target_id, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
-  const int bad0 = INT_MAX;
-  HIPCHK(hipMemcpyAsync(d_bad.p, &bad0, 4, hipMemcpyHostToDevice, st));
   HIPCHK(clk.mark(0, st));
-  FoldCsr f{};
-  f.key = d_key.as<uint64_t>();
-  f.key_sorted = d_keys.as<uint64_t>();
-  f.val_sorted = d_vals.as<float>();
-  f.hi = d_hi.as<uint32_t>();
-  f.col = d_col.as<uint32_t>();
-  f.runs = d_runs.as<uint32_t>();
-  f.counts = d_cnt.as<int32_t>();
-  f.ptr = d_ptr.as<int64_t>();
-  f.n_rows = d_nr.as<int64_t>();
-  f.ids = d_ids.as<int32_t>();
-  f.deg = d_deg.as<uint32_t>();
-  f.deg_sorted = d_degs.as<uint32_t>();
-  f.iota = d_iota.as<int32_t>();
-  f.order = d_order.as<int32_t>();
-  int64_t nr = 0;
-  HIPCHK(fold_build_csr(d_row.as<int32_t>(), d_src.as<int32_t>(), d_val.as<float>(), n, d_sids.as<int32_t>(), S.n,
-                        d_tmp.p, tb, f, &nr, st));
+  TRYC(F.build_csr(c));
   ExplainPairs x{};
   x.key = p_key.as<uint64_t>();
   x.key_sorted = p_keys.as<uint64_t>();
@@ -105,64 +70,36 @@ int explain(als_ctx* c, int side, double reg, double alpha, int implicit, int64_
   x.iota = p_iota.as<int32_t>();
   x.order = p_order.as<int32_t>();
   int64_t nu = 0;
-  HIPCHK(explain_map_pairs(p_row.as<int32_t>(), p_tgt.as<int32_t>(), n_pairs, f.ids, f.deg, nr, d_sids.as<int32_t>(), S.n,
-                           d_tmp.p, tb, x, &nu, st));
+  HIPCHK(explain_map_pairs(p_row.as<int32_t>(), p_tgt.as<int32_t>(), n_pairs, F.f.ids, F.f.deg, F.n_rows,
+                           F.d_sids.as<int32_t>(), c->s[1 - side].n, F.d_tmp.p, F.temp_bytes, x, &nu, st));
   HIPCHK(launch_explain_fill(n_pairs, m, d_total.as<double>(), d_oids.as<int32_t>(), d_contrib.as<double>(), st));
   HIPCHK(clk.mark(1, st));
-  const bool form_gram = implicit && !S.fold_gram_valid;
-  if (form_gram) {  // the fold-in's cache, by the fold-in's rule
-    const int nblk = audit_gram_blocks(S.n);
-    HIPCHK(d_slab.ensure((size_t)nblk * KP * KP * 8));
-    HIPCHK(S.d_foldG.ensure((size_t)KP * KP * 8));
-    HIPCHK(launch_audit_gram(KP, S.d_orig.as<float>(), S.n, d_slab.as<double>(), nblk, S.d_foldG.as<double>(), st));
-  }
+  TRYC(F.gram(c, implicit));
   HIPCHK(clk.mark(2, st));
-  const int n_wg = fold_workgroups(KP, nu, c->n_cu);
-  const size_t sd = fold_scratch_doubles(KP, n_wg);
-  if (sd) HIPCHK(d_scratch.ensure(sd * 8));
   ExplainArgs a{};
-  a.f.Y = S.d_orig.as<float>();
-  a.f.G = implicit ? S.d_foldG.as<double>() : nullptr;
-  a.f.ptr = f.ptr;
-  a.f.deg = f.deg;
-  a.f.col = f.col;
-  a.f.val = f.val_sorted;
-  a.f.k = k;
-  a.f.implicit = implicit;
-  a.f.alpha = alpha;
-  a.f.reg = reg;
-  a.f.scratch = sd ? d_scratch.as<double>() : nullptr;
-  a.f.bad = d_bad.as<int>();
+  int n_wg = 0;
+  TRYC(F.plan(c, nu, reg, alpha, implicit, &a.f, &n_wg));
   a.runs = x.runs;
   a.pptr = x.ptr;
   a.order = x.order;
   a.n_runs = nu;
   a.slot = x.slot;
   a.target = x.target;
-  a.src_ids = d_sids.as<int32_t>();
+  a.src_ids = F.d_sids.as<int32_t>();
   a.m = m;
   a.total = d_total.as<double>();
   a.ids = d_oids.as<int32_t>();
   a.contrib = d_contrib.as<double>();
-  HIPCHK(launch_explain(KP, a, n_wg, st));
+  HIPCHK(launch_explain(c->KP, a, n_wg, st));
   HIPCHK(clk.mark(3, st));
   int bad = INT_MAX;
-  HIPCHK(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&bad, F.d_bad.p, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (form_gram) S.fold_gram_valid = true;
   c->explain_ms[0] = event_ms(clk.e[0], clk.e[1]);
-  c->explain_ms[1] = form_gram ? event_ms(clk.e[1], clk.e[2]) : 0.0;
+  c->explain_ms[1] = F.form_gram ? event_ms(clk.e[1], clk.e[2]) : 0.0;
   c->explain_ms[2] = event_ms(clk.e[2], clk.e[3]);
   c->explain_ms[3] = event_ms(clk.e[0], clk.e[3]);
-  if (bad != INT_MAX) {
-    int32_t id = 0;
-    HIPCHK(copy_st(c, &id, f.ids + bad, 4, hipMemcpyDeviceToHost));
-    return fail(ALS_E_NOT_POSITIVE_DEFINITE,
-                "LAPACK.dppsv-equivalent Cholesky met a non-positive pivot because A is not positive definite. Is A "
-                "derived from a singular matrix (e.g. collinear column values)? (explanation of " +
-                    std::string(side == ALS_USER ? "user" : "item") + " " + std::to_string(id) +
-                    ", the lowest failing id)");
-  }
+  TRYC(F.finish(c, bad, "explanation"));
   HIPCHK(copy_st(c, total_out, d_total.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
   HIPCHK(copy_st(c, src_ids_out, d_oids.p, (size_t)n_pairs * m * 4, hipMemcpyDeviceToHost));
   HIPCHK(copy_st(c, contrib_out, d_contrib.p, (size_t)n_pairs * m * 8, hipMemcpyDeviceToHost));

@@ -30,14 +30,13 @@
 //     in the packed triangle (LDS at KP <= 128, the scratch slab at KP = 256) and fold_nnls iterates on it.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
 #include "fold_front.h"
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
@@ -46,28 +45,12 @@ namespace {
 
 constexpr uint32_t FOLD_DROPPED = 0xFFFFFFFFu;
 
-inline int fold_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
-
 __global__ void fold_key_kernel(const int32_t* __restrict__ row_id, const int32_t* __restrict__ src_id, int64_t n,
                                 const int32_t* __restrict__ ids, int64_t n_ids, uint64_t* __restrict__ key) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t v = src_id[i];
-    int64_t lo = 0, hi = n_ids;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (ids[mid] < v) lo = mid + 1;
-      else hi = mid;
-    }
-    const uint32_t c = (lo < n_ids && ids[lo] == v) ? (uint32_t)lo : FOLD_DROPPED;
+    const int64_t r = find_id(ids, n_ids, src_id[i]);
+    const uint32_t c = r >= 0 ? (uint32_t)r : FOLD_DROPPED;
     key[i] = ((uint64_t)((uint32_t)row_id[i] ^ 0x80000000u) << 32) | c;
-  }
-}
-
-__global__ void fold_split_kernel(const uint64_t* __restrict__ key, int64_t n, uint32_t* __restrict__ hi,
-                                  uint32_t* __restrict__ col) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    hi[i] = (uint32_t)(key[i] >> 32);
-    col[i] = (uint32_t)key[i];
   }
 }
 
@@ -86,11 +69,6 @@ __global__ void fold_rows_kernel(const uint32_t* __restrict__ runs, const int64_
     deg[r] = (uint32_t)(lo - p0);
     ids[r] = (int32_t)(runs[r] ^ 0x80000000u);
   }
-}
-
-__global__ void fold_iota_kernel(int32_t* __restrict__ out, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (int32_t)i;
 }
 
 // ---- the solve (its LDS layout, build and factorisation: fold_front.h) -----------------------------------
@@ -388,48 +366,28 @@ hipError_t fold_launch(const FoldArgs& a, int n_wg, hipStream_t s) {
 }  // namespace
 
 size_t fold_sort_temp_bytes(int64_t n) {
-  size_t a = 0, b = 0, c = 0, d = 0;
+  size_t a = 0;
   (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (float*)nullptr, (float*)nullptr,
                                   (size_t)n, 0, 64, (hipStream_t)0);
-  (void)rocprim::run_length_encode(nullptr, b, (uint32_t*)nullptr, (size_t)n, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                   (int64_t*)nullptr, (hipStream_t)0);
-  (void)rocprim::exclusive_scan(nullptr, c, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1,
-                                rocprim::plus<int64_t>(), (hipStream_t)0);
-  (void)rocprim::radix_sort_pairs_desc(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                       (int32_t*)nullptr, (size_t)n, 0, 32, (hipStream_t)0);
-  return std::max(std::max(a, b), std::max(c, d));
+  return std::max(a, group_temp_bytes<true, true>(n));
 }
 
 hipError_t fold_build_csr(const int32_t* row_id, const int32_t* src_id, const float* rating, int64_t n,
                           const int32_t* src_ids, int64_t n_src, void* temp, size_t temp_bytes, const FoldCsr& f,
                           int64_t* n_rows_host, hipStream_t s) {
   if (n <= 0 || n > (int64_t)0x7FFFFFFF || n_src >= (int64_t)FOLD_DROPPED) return hipErrorInvalidValue;
-  fold_key_kernel<<<fold_grid(n), 256, 0, s>>>(row_id, src_id, n, src_ids, n_src, f.key);
+  fold_key_kernel<<<front_grid(n), 256, 0, s>>>(row_id, src_id, n, src_ids, n_src, f.key);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   size_t tb = temp_bytes;
   e = rocprim::radix_sort_pairs(temp, tb, f.key, f.key_sorted, rating, f.val_sorted, (size_t)n, 0, 64, s);
   if (e != hipSuccess) return e;
-  fold_split_kernel<<<fold_grid(n), 256, 0, s>>>(f.key_sorted, n, f.hi, f.col);
-  e = hipMemsetAsync(f.counts, 0, (size_t)(n + 1) * 4, s);
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  e = rocprim::run_length_encode(temp, tb, f.hi, (size_t)n, f.runs, f.counts, f.n_rows, s);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(n_rows_host, f.n_rows, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  split_keys_kernel<<<front_grid(n), 256, 0, s>>>(f.key_sorted, n, f.hi, f.col);
+  e = group_runs<true>(temp, temp_bytes, f.hi, n, f.runs, f.counts, f.ptr, f.n_rows, n_rows_host, s);
   if (e != hipSuccess) return e;
   const int64_t nr = *n_rows_host;
-  if (nr <= 0 || nr > n) return hipErrorInvalidValue;
-  tb = temp_bytes;
-  e = rocprim::exclusive_scan(temp, tb, f.counts, f.ptr, (int64_t)0, (size_t)nr + 1, rocprim::plus<int64_t>(), s);
-  if (e != hipSuccess) return e;
-  fold_rows_kernel<<<fold_grid(nr), 256, 0, s>>>(f.runs, f.ptr, f.col, nr, f.ids, f.deg);
-  fold_iota_kernel<<<fold_grid(nr), 256, 0, s>>>(f.iota, nr);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  tb = temp_bytes;
-  return rocprim::radix_sort_pairs_desc(temp, tb, f.deg, f.deg_sorted, f.iota, f.order, (size_t)nr, 0, 32, s);
+  fold_rows_kernel<<<front_grid(nr), 256, 0, s>>>(f.runs, f.ptr, f.col, nr, f.ids, f.deg);
+  return degree_order<true>(temp, temp_bytes, f.deg, f.deg_sorted, f.iota, f.order, nr, s);
 }
 
 // KP = 64: one wave per row (its barriers cost nothing) and 19 KB of LDS, eight rows per CU; KP = 128: 69 KB

@@ -397,7 +397,8 @@ struct FoldCsr {
   int32_t *iota, *order;       // [n] order: the rows by descending degree (ties: ascending id)
 };
 size_t fold_sort_temp_bytes(int64_t n);
-// map + sort + run lengths + degrees + solve order of n > 0 triples; *n_rows_host is valid on return
+// map + sort + run lengths + degrees + solve order of n > 0 triples (id_front.h: find_id, split_keys_kernel,
+// group_runs, degree_order); *n_rows_host is valid on return
 hipError_t fold_build_csr(const int32_t* row_id, const int32_t* src_id, const float* rating, int64_t n,
                           const int32_t* src_ids, int64_t n_src, void* temp, size_t temp_bytes, const FoldCsr& f,
                           int64_t* n_rows_host, hipStream_t s);
@@ -444,7 +445,8 @@ struct ExplainPairs {
 };
 size_t explain_sort_temp_bytes(int64_t n_pairs);
 // map + sort + run lengths + solve order of n_pairs > 0 pairs over the CSR rows row_ids [n_rows] (FoldCsr::ids,
-// ascending) with degrees row_deg; *n_runs_host is valid on return
+// ascending) with degrees row_deg, through the same id_front.h pieces as fold_build_csr; *n_runs_host is valid
+// on return
 hipError_t explain_map_pairs(const int32_t* pair_row_id, const int32_t* pair_target_id, int64_t n_pairs,
                              const int32_t* row_ids, const uint32_t* row_deg, int64_t n_rows, const int32_t* src_ids,
                              int64_t n_src, void* temp, size_t temp_bytes, const ExplainPairs& e, int64_t* n_runs_host,

@@ -3,8 +3,9 @@
 // (fp32 products added left to right, multiply and add rounded separately), the best k are kept in
 // (score desc, row asc) order; NaN scores are never listed.
 //
-// Written like audit.hip and foldin.hip: a self-contained path beside the tuned one (topk.hip) that must
-// not disturb, or depend on, it.  Plain HIP, no inline asm, no MFMA, none of device_common.h.
+// Written like audit.hip and foldin.hip: a path beside the tuned one (topk.hip) that must not disturb, or
+// depend on, it.  Plain HIP, no inline asm, no MFMA, none of device_common.h; the id search and the grid
+// helper are id_front.h's.
 //
 //   query_excl_key_kernel  raw exclusion ids to dst rows by binary search; key (query << 32 | row), row
 //                          0xFFFFFFFF for an id the model does not know.  One 64-bit radix sort then leaves
@@ -27,6 +28,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
@@ -40,8 +42,6 @@ constexpr int QT_MERGE_AHEAD = 8;       // 64-entry loads of the merge in flight
 static_assert(QT_Q % QT_WAVES == 0 && QT_Q % 4 == 0, "query tile and waves do not match");
 static_assert(QT_Q * QT_ROWS <= QT_ROWS * QT_LD, "the scores of a tile take the place of the tile");
 
-inline int query_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384)); }
-
 __global__ void query_excl_key_kernel(const int64_t* __restrict__ excl_ptr, int64_t n_q, const int32_t* __restrict__ excl_ids,
                                       int64_t n_e, const int32_t* __restrict__ ids, int64_t n_ids,
                                       uint64_t* __restrict__ key) {
@@ -52,16 +52,8 @@ __global__ void query_excl_key_kernel(const int64_t* __restrict__ excl_ptr, int6
       if (excl_ptr[mid + 1] <= i) lo = mid + 1;
       else hi = mid;
     }
-    const uint64_t q = (uint64_t)lo;
-    const int32_t v = excl_ids[i];
-    lo = 0, hi = n_ids;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (ids[mid] < v) lo = mid + 1;
-      else hi = mid;
-    }
-    const uint32_t r = (lo < n_ids && ids[lo] == v) ? (uint32_t)lo : QT_NOROW;
-    key[i] = (q << 32) | r;
+    const int64_t r = find_id(ids, n_ids, excl_ids[i]);
+    key[i] = ((uint64_t)lo << 32) | (r >= 0 ? (uint32_t)r : QT_NOROW);
   }
 }
 
@@ -261,11 +253,7 @@ __global__ __launch_bounds__(256) void query_merge_kernel(const float* __restric
 
 }  // namespace
 
-size_t query_sort_temp_bytes(int64_t n_e) {
-  size_t a = 0;
-  (void)rocprim::radix_sort_keys(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n_e, 0, 64, (hipStream_t)0);
-  return a;
-}
+size_t query_sort_temp_bytes(int64_t n_e) { return sort_keys64_temp_bytes(n_e); }
 
 hipError_t query_map_exclusions(const int64_t* excl_ptr, int64_t n_q, const int32_t* excl_ids, int64_t n_e,
                                 const int32_t* dst_ids, int64_t n_dst, uint64_t* key, uint64_t* key_sorted, void* temp,
@@ -273,7 +261,7 @@ hipError_t query_map_exclusions(const int64_t* excl_ptr, int64_t n_q, const int3
   if (n_e <= 0) return hipSuccess;
   if (n_e > (int64_t)0x7FFFFFFF || n_q <= 0 || n_q > (int64_t)0x7FFFFFFF || n_dst >= (int64_t)QT_NOROW)
     return hipErrorInvalidValue;
-  query_excl_key_kernel<<<query_grid(n_e), 256, 0, s>>>(excl_ptr, n_q, excl_ids, n_e, dst_ids, n_dst, key);
+  query_excl_key_kernel<<<front_grid(n_e), 256, 0, s>>>(excl_ptr, n_q, excl_ids, n_e, dst_ids, n_dst, key);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   size_t tb = temp_bytes;
@@ -327,7 +315,7 @@ hipError_t launch_query_merge(const float* part_score, const uint32_t* part_row,
                               const int32_t* dst_ids, int32_t* ids_out, float* scores_out, hipStream_t s) {
   if (n_q <= 0) return hipSuccess;
   if (k < 1 || k > 64 || n_slices < 1) return hipErrorInvalidValue;
-  query_merge_kernel<<<query_grid(n_q * 64), 256, 0, s>>>(part_score, part_row, n_slices, n_q, k, dst_ids, ids_out,
+  query_merge_kernel<<<front_grid(n_q * 64), 256, 0, s>>>(part_score, part_row, n_slices, n_q, k, dst_ids, ids_out,
                                                           scores_out);
   return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 // als_similar / als_similar_vectors: cosine top-k of one side against itself (similar.hip holds the kernels).
 // Both calls build the side's unit image on the device and hand it to a scan the project already has:
-//   scan tier    launch_query_scan / launch_query_merge of query_topk.hip, the unit image as Y, the gathered
-//                unit rows as queries and each query's own row as its one exclusion;
+//   scan tier    scan_lists of query_topk_host.cpp (launch_query_scan / launch_query_merge), the unit image as Y,
+//                the gathered unit rows as queries and each query's own row as its one exclusion;
 //   passes tier  a transient model-only context whose two sides both view the unit image (restricted to the
 //                rows that have a direction, which keeps it inside als_recommend_unseen's finite-factor
 //                contract), served by als_recommend_unseen with the pairs (id, id).  The context lives and
@@ -71,33 +71,12 @@ void pad_lists(int32_t* ids, float* scores, int64_t n) {
   std::fill(scores, scores + n, NAN);
 }
 
-// The scan tier behind both entry points: every buffer is the caller's, on the device; the lists land in
-// ids_out / scores_out on the host.  Marks 3 (scan done) and 4 (merge done) are recorded here
-int scan_lists(als_ctx* c, const Side& S, int k, const float* d_unit, const float* d_q, int64_t n_q, const int64_t* d_ptr,
-               const uint64_t* d_keys, const int32_t* d_ids, Marks<5>& clk, int32_t* ids_out, float* scores_out) {
-  hipStream_t st = c->st;
-  const QueryPlan plan = query_plan(S.n, n_q, c->n_cu);
-  DevBuf d_ps, d_pr, d_oi, d_os;
-  Drain queued{st};
-  const size_t part = (size_t)plan.n_slices * n_q * k;
-  HIPCHK(d_ps.ensure(part * 4));
-  HIPCHK(d_pr.ensure(part * 4));
-  HIPCHK(d_oi.ensure((size_t)n_q * k * 4));
-  HIPCHK(d_os.ensure((size_t)n_q * k * 4));
-  HIPCHK(launch_query_scan(c->KP, c->p.rank, d_unit, S.n, d_q, n_q, k, d_ptr, d_keys, plan, d_ps.as<float>(),
-                           d_pr.as<uint32_t>(), c->n_cu, st));
-  HIPCHK(clk.mark(3, st));
-  HIPCHK(launch_query_merge(d_ps.as<float>(), d_pr.as<uint32_t>(), plan.n_slices, n_q, k, d_ids, d_oi.as<int32_t>(),
-                            d_os.as<float>(), st));
-  HIPCHK(clk.mark(4, st));
-  HIPCHK(hipMemcpyAsync(ids_out, d_oi.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(scores_out, d_os.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+// similar_ms of a scan-tier call from its five marks: 0 start, 1 unit image, 2 queries, 3 scan, 4 merge
+void scan_timing(als_ctx* c, const Marks<5>& clk) {
   c->similar_ms[0] = event_ms(clk.e[0], clk.e[2]);
   c->similar_ms[1] = event_ms(clk.e[2], clk.e[3]);
   c->similar_ms[2] = event_ms(clk.e[3], clk.e[4]);
   c->similar_ms[3] = event_ms(clk.e[0], clk.e[4]);
-  return ALS_OK;
 }
 
 // The side's unit image and direction flags on c->st (queued); the side is materialised
@@ -117,6 +96,7 @@ int similar_scan(als_ctx* c, int side, int k, const int32_t* rows, int64_t nq, i
   hipStream_t st = c->st;
   const int rank = c->p.rank;
   DevBuf d_unit, d_flag, d_rows, d_q, d_ptr, d_keys, d_ids;
+  ScanBuffers B;
   Marks<5> clk;
   std::vector<int32_t> flag((size_t)S.n);
   Drain queued{st};
@@ -136,8 +116,10 @@ int similar_scan(als_ctx* c, int side, int k, const int32_t* rows, int64_t nq, i
                                nq, d_q.as<float>(), d_ptr.as<int64_t>(), d_keys.as<uint64_t>(), st));
   HIPCHK(clk.mark(2, st));
   if (S.n > 0) HIPCHK(hipMemcpyAsync(flag.data(), d_flag.p, (size_t)S.n * 4, hipMemcpyDeviceToHost, st));
-  TRYC(scan_lists(c, S, k, d_unit.as<float>(), d_q.as<float>(), nq, d_ptr.as<int64_t>(), d_keys.as<uint64_t>(),
-                  d_ids.as<int32_t>(), clk, ids_out, scores_out));
+  TRYC(B.ensure(c, S.n, nq, k));  // behind mark 2, where these allocations have always stood
+  TRYC(scan_lists(c, B, k, d_unit.as<float>(), S.n, d_q.as<float>(), nq, d_ptr.as<int64_t>(), d_keys.as<uint64_t>(),
+                  d_ids.as<int32_t>(), &clk.e[3], &clk.e[4], ids_out, scores_out));
+  scan_timing(c, clk);
   c->similar_stats[1] = count_zero(flag);
   return ALS_OK;
 }
@@ -258,8 +240,9 @@ int similar_vectors(als_ctx* c, int side, int k, int64_t n_q, const float* q, co
   Side& S = c->s[side];
   hipStream_t st = c->st;
   const int rank = c->p.rank;
-  const int64_t n_e = ptr0.empty() ? 0 : ptr0.back();
-  DevBuf d_unit, d_flag, d_raw, d_q, d_ids, d_ptr, d_eid, d_key, d_keys, d_tmp;
+  DevBuf d_unit, d_flag, d_raw, d_q, d_ids;
+  Exclusions X;
+  ScanBuffers B;
   Marks<5> clk;
   std::vector<int32_t> flag((size_t)S.n);
   Drain queued{st};
@@ -268,28 +251,18 @@ int similar_vectors(als_ctx* c, int side, int k, int64_t n_q, const float* q, co
   HIPCHK(d_ids.ensure((size_t)std::max<int64_t>(S.n, 1) * 4));
   HIPCHK(hipMemcpyAsync(d_raw.p, q, (size_t)n_q * rank * 4, hipMemcpyHostToDevice, st));
   if (S.n > 0) HIPCHK(hipMemcpyAsync(d_ids.p, S.ids.data(), (size_t)S.n * 4, hipMemcpyHostToDevice, st));
-  size_t tb = 0;
-  if (n_e > 0) {
-    tb = query_sort_temp_bytes(n_e);
-    HIPCHK(d_ptr.ensure((size_t)(n_q + 1) * 8));
-    HIPCHK(d_eid.ensure((size_t)n_e * 4));
-    HIPCHK(d_key.ensure((size_t)n_e * 8));
-    HIPCHK(d_keys.ensure((size_t)n_e * 8));
-    HIPCHK(d_tmp.ensure(std::max<size_t>(tb, 16)));
-    HIPCHK(hipMemcpyAsync(d_ptr.p, ptr0.data(), (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_eid.p, excl_ids, (size_t)n_e * 4, hipMemcpyHostToDevice, st));
-  }
+  TRYC(X.upload(c, n_q, ptr0, excl_ids));
   HIPCHK(clk.mark(0, st));
   TRYC(unit_image(c, S, d_unit, d_flag));
   HIPCHK(clk.mark(1, st));
   HIPCHK(launch_similar_unit(d_raw.as<float>(), rank, n_q, rank, d_q.as<float>(), rank, nullptr, st));
-  if (n_e > 0)
-    HIPCHK(query_map_exclusions(d_ptr.as<int64_t>(), n_q, d_eid.as<int32_t>(), n_e, d_ids.as<int32_t>(), S.n,
-                                d_key.as<uint64_t>(), d_keys.as<uint64_t>(), d_tmp.p, tb, st));
+  TRYC(X.map(c, n_q, d_ids.as<int32_t>(), S.n));
   HIPCHK(clk.mark(2, st));
   if (S.n > 0) HIPCHK(hipMemcpyAsync(flag.data(), d_flag.p, (size_t)S.n * 4, hipMemcpyDeviceToHost, st));
-  TRYC(scan_lists(c, S, k, d_unit.as<float>(), d_q.as<float>(), n_q, n_e > 0 ? d_ptr.as<int64_t>() : nullptr,
-                  n_e > 0 ? d_keys.as<uint64_t>() : nullptr, d_ids.as<int32_t>(), clk, ids_out, scores_out));
+  TRYC(B.ensure(c, S.n, n_q, k));  // behind mark 2, as in similar_scan
+  TRYC(scan_lists(c, B, k, d_unit.as<float>(), S.n, d_q.as<float>(), n_q, X.ptr(), X.keys(), d_ids.as<int32_t>(),
+                  &clk.e[3], &clk.e[4], ids_out, scores_out));
+  scan_timing(c, clk);
   c->similar_stats[1] = count_zero(flag);
   return ALS_OK;
 }
@@ -343,22 +316,7 @@ extern "C" int als_similar_vectors(als_ctx* c, int dst_side, int32_t k, int64_t 
   if (c->world > 1) return fail(ALS_E_UNSUPPORTED, "als_similar_vectors is single-process (world = 1)");
   if (n_q > (int64_t)0x7FFFFFFF) return fail(ALS_E_UNSUPPORTED, "als_similar_vectors takes at most 2^31 - 1 queries a call");
   std::vector<int64_t> ptr0;
-  if (excl_ptr && n_q > 0) {
-    if (excl_ptr[0] < 0) return fail(ALS_E_INVALID_ARGUMENT, "als_similar_vectors: excl_ptr is negative");
-    for (int64_t i = 0; i < n_q; ++i)
-      if (excl_ptr[i + 1] < excl_ptr[i])
-        return fail(ALS_E_INVALID_ARGUMENT, "als_similar_vectors: excl_ptr does not ascend at query " + std::to_string(i));
-    const int64_t n_e = excl_ptr[n_q] - excl_ptr[0];
-    if (n_e > (int64_t)0x7FFFFFFF)
-      return fail(ALS_E_UNSUPPORTED, "als_similar_vectors takes at most 2^31 - 1 exclusions a call");
-    if (n_e > 0 && !excl_ids)
-      return fail(ALS_E_INVALID_ARGUMENT, "als_similar_vectors: excl_ids is null and excl_ptr names a non-empty range");
-    if (n_e > 0) {
-      ptr0.resize((size_t)n_q + 1);
-      for (int64_t i = 0; i <= n_q; ++i) ptr0[(size_t)i] = excl_ptr[i] - excl_ptr[0];
-      excl_ids += excl_ptr[0];
-    }
-  }
+  TRYC(exclusion_ranges("als_similar_vectors", ALS_E_UNSUPPORTED, n_q, excl_ptr, &excl_ids, &ptr0));
   for (double& v : c->similar_ms) v = 0.0;
   for (int64_t& v : c->similar_stats) v = 0;
   if (n_q == 0) return ALS_OK;

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <string>
 #include "device_common.h"
+#include "id_front.h"
 #include "kernels.h"
 
 namespace albedo {
@@ -1516,20 +1517,11 @@ __device__ __forceinline__ bool unseen_has_id(const UnseenExcl& x, int64_t e0, i
   return lo < e1 && dst_ids[unseen_row_at(x, lo)] == id;
 }
 
-__device__ __forceinline__ int64_t unseen_find_id(const int32_t* __restrict__ ids, int64_t n, int32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && ids[lo] == v ? lo : -1;
-}
 __global__ void unseen_pair_key_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ edst, int64_t n_e,
                                        const int32_t* __restrict__ src_ids, int64_t n_src,
                                        const int32_t* __restrict__ dst_ids, int64_t n_dst, uint64_t* __restrict__ key) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t u = unseen_find_id(src_ids, n_src, esrc[i]), d = unseen_find_id(dst_ids, n_dst, edst[i]);
+    const int64_t u = find_id(src_ids, n_src, esrc[i]), d = find_id(dst_ids, n_dst, edst[i]);
     key[i] = (u < 0 || d < 0) ? ~(uint64_t)0 : ((uint64_t)u << 32) | (uint64_t)d;
   }
 }
@@ -1705,12 +1697,7 @@ __global__ __launch_bounds__(256) void unseen_exact_kernel(TopkArgs a, UnseenExc
   if (scored && lane == 0 && n_scored) atomicAdd(scored, n_scored);
 }
 
-size_t unseen_sort_temp_bytes(int64_t n_e) {
-  size_t a = 0;
-  (void)rocprim::radix_sort_keys(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max<int64_t>(n_e, 1), 0, 64,
-                                 (hipStream_t)0);
-  return a;
-}
+size_t unseen_sort_temp_bytes(int64_t n_e) { return sort_keys64_temp_bytes(std::max<int64_t>(n_e, 1)); }
 
 hipError_t unseen_pair_ranges(const int32_t* esrc, const int32_t* edst, int64_t n_e, const int32_t* src_ids, int64_t n_src,
                               const int32_t* dst_ids, int64_t n_dst, uint64_t* key, uint64_t* key_sorted, void* temp,

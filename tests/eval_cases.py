@@ -29,7 +29,7 @@ I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
 LENGTHS = [1, 29, 30, 31, 63, 64, 65, 127, 128, 129, 200, 1000]
 LENGTH_VARIANTS = ["random", "ties", "last64"]
 CATALOGUES = ["negative", "mixed", "extreme", "five", "twentynine"]
-MAP_CAP = 16384 * 256                 # eval.hip ev_grid: at most 16384 blocks of 256 threads
+MAP_CAP = 16384 * 256                 # id_front.h front_grid: at most 16384 blocks of 256 threads
 N_PAST_CAP = MAP_CAP + 257
 BIG = 1 << 60                         # BIG and BIG + 1 are one float64
 PASS_ROWS = 1 << 16                   # the smallest ALBEDO_TOPK_PASS the engine accepts
